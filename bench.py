@@ -6,9 +6,17 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = forward + backward + gradient all-reduce (N>1) + AMSGrad update on one synthetic batch that is
-already resident in HBM.  Rank 0 prints ONE JSON line.  The `roofline` object is measured with HIP events
-around every launch of the dominant kernel inside the timed region; `cpu_baseline` times the torch-CPU restatement
-of the same step (oracle/torch_step.py, float32, all host threads, batch 64) on rank 0 at N=1 only.
+already resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and
+reports the headline (`value`, `ms_per_step`, ...) and nothing else.  With --full it also measures what goes
+around the headline: the `roofline` object (per-launch timings of the dominant kernel, from device-clock stamps in a
+second capture of the step, or HIP events when eager), the kernels timed alone, the fine-tuning step and the native
+f32 MFMA step (`secondary`) and `cpu_baseline`, the torch-CPU restatement of the same step (oracle/torch_step.py,
+float32, all host threads, batch 64) on rank 0 at N=1 only.
+
+--dump-outputs DIR writes, right after the timed steps, what the last timed step handed its caller: the cost
+(`cost.npy`, float64) and every trainable variable after the update (`<name with / as .>.npy`, float32).  Past 64 MB
+in all, large variables are written as a fixed sample of their flattened entries (sorted indices drawn by
+numpy RandomState(0)).  Inputs and initial weights are seeded, so two runs with the same arguments start alike.
 """
 from __future__ import print_function
 
@@ -56,6 +64,10 @@ def parse():
     ap.add_argument('--chunk', type=int, default=20480)
     ap.add_argument('--filters', type=int, default=256)
     ap.add_argument('--quiet', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline / standalone kernels, the secondary steps and the CPU baseline (off: headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's cost and updated trainable variables to DIR/<name>.npy")
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -217,6 +229,35 @@ def cpu_baseline_guarded(args):
         return {'value': None, 'unit': 'mixtures/s', 'cores': None, 'kind': 'port', 'sample': 'not measured: %s: %s' % (type(e).__name__, e)}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(folder, cost, variables):
+    """What the caller of the timed step receives from its last call: the cost (float64) and the trainable variables the optimizer
+    just updated (float32), one .npy per array.  If they exceed DUMP_BUDGET_BYTES, every variable above a common size cap is cut to
+    a fixed sample of that many flattened entries (sorted indices from RandomState(0)): the same entries on every run and build."""
+    import numpy as np
+    arrays = [('cost', np.array([cost], dtype=np.float64))]
+    arrays += [(v.ams_name.replace('/', '.'), v.detach().float().cpu().numpy()) for v in variables]
+    header = 128                                                   # .npy header of a small-rank array
+    room = (DUMP_BUDGET_BYTES - header * len(arrays)) // 4
+    sizes = sorted(a.size for _, a in arrays)
+    cap = sizes[-1]
+    if sum(sizes) > room:
+        # largest cap with sum(min(size, cap)) <= room: whole arrays below it, samples of `cap` entries above it
+        used = 0
+        for i, n in enumerate(sizes):
+            if used + n * (len(sizes) - i) > room:
+                cap = (room - used) // (len(sizes) - i)
+                break
+            used += n
+    os.makedirs(folder, exist_ok=True)
+    for name, a in arrays:
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(folder, name + '.npy'), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -288,7 +329,7 @@ def main():
         torch.cuda.synchronize()
         dist.barrier()
         torch.cuda.synchronize()
-        ops.PROFILE.reset(enabled=not args.graph)
+        ops.PROFILE.reset(enabled=args.full and not args.graph)
         opt_ = model.optimize
         if world > 1:
             opt_.exchange_events = []                # HIP events around the gradient all-reduce of every timed step
@@ -308,8 +349,10 @@ def main():
         last_cost = float(c)
         if last_cost != last_cost or last_cost in (float('inf'), float('-inf')):
             raise SystemExit('bench.py: the timed steps ended with cost %r -- a diverged step is not a measurement' % last_cost)
+        if args.dump_outputs and rank == 0:                # (the replicas hold the same weights)
+            dump_outputs(args.dump_outputs, last_cost, model.trainable_variables)
         prof_steps = args.steps
-        if args.graph and args.roofline_steps:
+        if args.full and args.graph and args.roofline_steps:
             # HIP events recorded during capture cannot be read back after a replay (hipErrorInvalidHandle), so the launches of the
             # dominant kernel are bracketed by device-clock STAMPS (ams_stamp, ops._Profile) in a SECOND capture of the same step:
             # same model, same batches, same streams and overlap as the timed graph, plus two one-thread kernels per timed launch.
@@ -335,7 +378,7 @@ def main():
         # The same launches timed ALONE (same model, same batches, side stream off, no cap) say what the kernel itself reaches.
         alone = None
         stamped_ms = locals().get('stamped_ms', 0.0)
-        if prof_steps and args.roofline_steps:
+        if args.full and prof_steps and args.roofline_steps:
             from ams_hip import functional as F
             was, main_prof = F.OVERLAP.enabled, ops.PROFILE
             F.OVERLAP.enabled = False
@@ -517,8 +560,10 @@ def main():
                                '3xBLSTM(600) -> dense 600->%d -> l2norm -> DPCL loss, fwd+bwd+AMSGrad' % (N, N * E),
                    'batch_per_gpu': B, 'global_batch': B * world, 'nb_speakers': S, 'chunk_size': L, 'frames': T,
                    'parallelism': 'dp%d' % world, 'hip_graph': bool(args.graph)},
-        'roofline': roof, 'roofline_hbm': roof_hbm, 'north_star_targets': targets, 'final_cost': last_cost,
+        'final_cost': last_cost,
     }
+    if args.full:
+        out.update(roofline=roof, roofline_hbm=roof_hbm, north_star_targets=targets)
     if ops.PS_TUNED:
         out['forward_products'] = dict(ops.PS_TUNED, note='the captured step was replayed both ways before the timed region and kept the faster form on this board: pre-split operand images (csrc/gemm_ps.hip) raise the matrix-pipe duty, and some boards then settle at a lower clock for the whole step (DESIGN.md 4.1b)')
     if world > 1:
@@ -527,7 +572,7 @@ def main():
         out['allreduce_bytes'] = int(model.optimize._gbuf.numel() * 4)
         out['comm'] = comm_record(dist, nccl_log if os.environ.get('NCCL_DEBUG_FILE') == nccl_log else os.environ.get('NCCL_DEBUG_FILE'))
     if rank == 0:
-        if world == 1 and not args.no_secondary and (B, L, N) == (64, 20480, 256):
+        if args.full and world == 1 and not args.no_secondary and (B, L, N) == (64, 20480, 256):
             # BASELINE configs[2] names the fine-tuning flavour of the same model; SURVEY 8(d) makes cfg3(i) the headline and
             # cfg3(ii) a second number: reported here for completeness, never as `value`
             try:
@@ -542,7 +587,7 @@ def main():
                                                                    'workload': r['workload']}}
             except Exception as e:                       # the headline line must still be printed
                 out['secondary'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if world == 1 and x6 and not args.no_native_f32:
+        if args.full and world == 1 and x6 and not args.no_native_f32:
             # the same timed region with the native f32 MFMA products (AMS_GEMM_X6=0), in a fresh process (the hipGraph is captured per arithmetic)
             import subprocess
             try:
@@ -557,7 +602,7 @@ def main():
                 out['value_native_f32'] = j['value']            # the headline metric under the reference's own product arithmetic
             except Exception as e:
                 out.setdefault('secondary', {})['native_f32_mfma'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_guarded(args)
         print(json.dumps(out))
 

@@ -1,5 +1,5 @@
-# copy one final_run's outputs from gpurun_out/ into profiles/ under its tag:  tools/collect_profiles.sh r05_k
-T=$1; G=gpurun_out; P=profiles
+# copy one final_run's outputs from prof_out/ (or $AMS_PROF_OUT) into profiles/ under its tag:  tools/collect_profiles.sh r05_k
+T=$1; G=${AMS_PROF_OUT:-prof_out}; P=profiles
 cp $G/${T}_bench.json $P/${T}_bench.json
 cp $G/kernel_stats_${T}.txt $P/${T}_kernel_stats.txt
 cp $(ls $G/step_timeline_${T}_*.txt | head -1) $P/${T}_step_timeline.txt

@@ -24,7 +24,7 @@ def write_json(db, out_json, commit):
     import json
     c = sqlite3.connect(db)
     rows = list(c.execute("select name, count(*), avg(duration) from kernels group by name order by sum(duration) desc"))
-    js = {'_meta': {'commit': commit, 'source': 'rocprofv3 --kernel-trace of `python bench.py --no-cpu-baseline --no-secondary` (hipGraph replay)'}}
+    js = {'_meta': {'commit': commit, 'source': 'rocprofv3 --kernel-trace of `python bench.py --full --no-cpu-baseline --no-secondary` (hipGraph replay)'}}
     for n, k, a in rows[:16]:
         key = n.replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0][:70]
         js[key] = {'calls': k, 'avg_us': round(a / 1e3, 2)}
