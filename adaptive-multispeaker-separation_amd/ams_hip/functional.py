@@ -285,7 +285,7 @@ class Dense(Function):
         if OVERLAP.usable(W, b) and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
             dx = None
             if _DENSE_MODE == 0 and _ORDER >= 1 and ctx.needs_input_grad[0]:
-                dx = ops.gemm(du2, W, transB=True, amax=am_dx).view(x.shape)
+                dx = ops.backward_product(du2, W, am_dx, W).view(x.shape)
             s = OVERLAP.fork(x2, du2)
             Nw = W.shape[1]
             cuts = _dw_cuts(Nw) if (_DENSE_MODE == 0 and ctx.needs_input_grad[0] and W.grad.stride(0) == Nw) else [(0, Nw)]
@@ -316,9 +316,9 @@ class Dense(Function):
                 # on the side stream when the recurrence below starts
                 torch.cuda.current_stream().wait_stream(s)
             if dx is None and ctx.needs_input_grad[0]:
-                dx = ops.gemm(du2, W, transB=True, amax=am_dx).view(x.shape)
+                dx = ops.backward_product(du2, W, am_dx, W).view(x.shape)
             return dx, None, None
-        dx = ops.gemm(du2, W, transB=True, amax=am_dx).view(x.shape) if ctx.needs_input_grad[0] else None
+        dx = ops.backward_product(du2, W, am_dx, W).view(x.shape) if ctx.needs_input_grad[0] else None
         dW = ops.gemm(x2, du2, transA=True, amax=am_dw) if ctx.needs_input_grad[1] else None
         db = ops.colsum(du2) if ctx.needs_input_grad[2] else None
         return dx, dW, db

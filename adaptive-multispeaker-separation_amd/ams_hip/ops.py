@@ -248,7 +248,7 @@ def _frozen(*ts):
 
 
 def drop_frozen_derivatives(t):
-    for k in ('_ams_amax_cache', '_ams_wcat', '_ams_wcat_amax', '_ams_kbound', '_ams_bcat', '_ams_ps_w'):
+    for k in ('_ams_amax_cache', '_ams_wcat', '_ams_wcat_amax', '_ams_kbound', '_ams_bcat', '_ams_ps_w', '_ams_ps_dx'):
         if hasattr(t, k):
             delattr(t, k)
 
@@ -737,6 +737,57 @@ def forward_product(x2, W2, bias, out, amax, label, owner, ldc=None):
     return gemm_ps(a_img, b_img, K, amax, bias=bias, out=out, ldc=ldc, label=label)
 
 
+# The backward input-gradient products dX = dU . W^T from a PS32 image of W (csrc/gemm_ps.hip: ams_gemm_ps_a_f32): same bits as the
+# in-product fp16x3 form, so it runs in both forms a captured step tunes between.  AMS_GEMM_DX_PS=0: the in-product form (A/B runs).
+DX_PS = _os.environ.get('AMS_GEMM_DX_PS', '1') != '0'
+
+
+def _ps_dx_weight_image(W2, amax_w, owner):
+    """PS32 image of W2 [N, K] itself (the B operand of dU . W2^T: no transpose), cut once per pass and kept across passes for frozen
+    weights; cached on `owner` beside (not in) the forward products' image of W2^T."""
+    c = getattr(owner, '_ams_ps_dx', None)
+    if (c is not None and c[1] == W2.data_ptr() and c[2] == tuple(W2.shape) and c[3] is amax_w and (c[0] == PASS[0] or _frozen(owner))):
+        return c[4]
+    img = ps_pack_rows(W2, amax_w)
+    owner._ams_ps_dx = (PASS[0], W2.data_ptr(), tuple(W2.shape), amax_w, img)
+    return img
+
+
+def backward_product(dU2, W2, amax, owner, out=None, label=''):
+    """out [M, N] = dU2 [M, K] . W2 [N, K]^T: the input gradients of the dense layer and of a BLSTM layer's input projection.  From a
+    pre-split image of W2 (cut once per pass, kept for frozen weights) with dU2 cut inside the product where both bounds are at hand,
+    fp16x3 is not denied for this product class (the key of the in-product form), no audit is in progress, no residency cap, and the
+    operands are 16-byte addressable; otherwise ams_gemm_f32."""
+    M, K = dU2.shape
+    N = W2.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dU2.device)
+    ldc = out.stride(0) if out.dim() == 2 else N
+    lda = dU2.stride(0)
+    key = ('gemm', label, M, N, K, False, True)
+    lib = load()
+    if not (DX_PS and F16X3 and amax is not None and amax[0] is not None and amax[1] is not None and key not in F16_AUDIT.denied
+            and not F16_AUDIT.active and LDS_PAD[0] == 0 and N % 4 == 0 and ldc % 4 == 0 and lda % 4 == 0 and dU2.stride(1) == 1
+            and W2.stride(1) == 1 and out.data_ptr() % 16 == 0 and dU2.data_ptr() % 16 == 0 and M * lda * 4 < 2 ** 31
+            and N * ((K + 31) // 32 * 128) < 2 ** 31 and lib.ams_gemm_get_arith() != 0
+            and K % 4 == 0 and (N + 255) // 256 * 256 <= 1.30 * N):
+        # (the last two: where the in-product form is fp16x3 -- 16-byte fetches -- on the same 128 x 256 tile, csrc/gemm.hip: launch,
+        # x6_choose_cfg, and so gives the same bits)
+        return gemm(dU2, W2, transB=True, out=out, M=M, N=N, K=K, lda=lda, ldb=W2.stride(0), ldc=ldc, label=label, amax=amax)
+    b_img = _ps_dx_weight_image(W2, amax[1], owner)
+    nb = lib.ams_gemm_ps_a_workspace_bytes(M, N, K)
+    ws = _ws(nb, dU2) if nb else None
+    ev = PROFILE.begin() if PROFILE.enabled else None
+    cur = torch.cuda.current_stream()
+    amax[0].record_stream(cur)
+    amax[1].record_stream(cur)
+    check(lib.ams_gemm_ps_a_f32(M, N, K, _p(dU2), lda, _p(b_img), _p(out), ldc, _p(amax[0]), _p(amax[1]), _p(ws), nb, _s()),
+          'ams_gemm_ps_a_f32')
+    if ev is not None:
+        PROFILE.end(ev, 2.0 * M * N * K, 4.0 * (M * K + K * N + M * N), 'gemm16ps_a<0,1>', label)
+    return out
+
+
 def gemm_at_b_colsum(A, B, out, bsum, accumulate=True, amax=None, ldc=None):
     """out[M,N] (+)= A^T B and bsum[N] (+)= column sums of B in ONE pass over B (A [K,M], B [K,N] row-major).  Returns False when
     the shapes / alignments do not allow the fused form (the caller then uses gemm + colsum)."""
@@ -1088,7 +1139,7 @@ def blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=None):
     M = B * T
     Wcat = blstm_wcat(Kf, Kb, D)
     dx = torch.empty((B, T, D), dtype=torch.float32, device=G.device)
-    gemm(G.view(-1), Wcat, transB=True, out=dx, M=M, N=D, K=8 * H, lda=8 * H, ldb=8 * H, ldc=D, amax=amax)
+    backward_product(G.view(M, 8 * H), Wcat, amax, Kf, out=dx.view(M, D))
     return dx
 
 

@@ -32,6 +32,10 @@ size_t conv_maxpool_ps_bytes(int Bt, int L, int W, int N);
 bool conv_maxpool_ps_applies(int Bt, int L, int W, int N);
 ams_status conv_maxpool_ps(const float* x, const float* f, float* pmax, int32_t* pidx, int Bt, int L, int W, int N, int pl,
                            const float* amax_x, const float* amax_f, void* img, hipStream_t st);
+// csrc/gemm.hip, used by csrc/gemm_ps.hip (ams_gemm_ps_a_f32): the k-split the in-product form's 128 x 256 tile takes for the same
+// product (cost model, k per split in *kps) and the slab reduce it runs -- the same partition and summation order, so the same bits
+int dx_splits(int M, int N, int K, size_t ws_bytes, int* kps);
+ams_status splitk_reduce(const float* partial, float* C, int M, int N, long ldc, int splits, hipStream_t st);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -1621,6 +1621,30 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+namespace ams_detail {
+
+// what launch() does for an uncapped fp16x3 launch on the 128 x 256 configuration (X6Cfg<3>) with ws_bytes of slabs
+__attribute__((visibility("hidden"))) int dx_splits(int M, int N, int K, size_t ws_bytes, int* kps) {
+    int splits = choose_splits(M, N, K, 1, x6_plan(3));
+    if (tuning().splits > 0) splits = tuning().splits;
+    while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
+    int k = ceil_div(ceil_div(K, splits), X6_BK) * X6_BK;
+    *kps = k;
+    return ceil_div(K, k);
+}
+
+// C = sum of the slabs partial[s] [M, N] in split order (N, ldc multiples of 4, 16-byte aligned C / partial)
+__attribute__((visibility("hidden"))) ams_status splitk_reduce(const float* partial, float* C, int M, int N, long ldc, int splits, hipStream_t st) {
+    const long total = (long)M * N;
+    if (N % 4 || ldc % 4 || (((uintptr_t)C | (uintptr_t)partial) & 15) || total >= (1L << 31)) return AMS_E_INVALID_ARG;
+    int blocks = (int)((total / 4 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3(blocks, 1), dim3(256), 0, st, partial, C, (const float*)nullptr, M, N, ldc, splits, 0, 0L, 0L);
+    return ams_check_launch();
+}
+
+}  // namespace ams_detail
+
 extern "C" {
 
 void ams_gemm_set_arith(int mode) { g_gemm_arith.store(mode ? 1 : 0, std::memory_order_relaxed); }

@@ -176,14 +176,23 @@ struct PsArgs {
     // the operand is the window xp[p .. p + K) of the zero-padded signal; A is the "shifted-copies" image of ps_pack_conv_kernel
     int conv_L, conv_R; unsigned conv_lpp; long a_bytes;
     int32_t* pidx;             // CONV: per (row tile, column) arg-max row, beside the maxima in C (the fused max-pool partial)
+    // AF32 (ams_gemm_ps_a_f32): A is f32 [M, K] with row pitch lda floats, cut inside the kernel; k is cut into `splits` ranges of kps
+    // (a multiple of 32) whose partial products go to slabs partial[split] [M, N] when splits > 1
+    const float* Af; long lda;
+    int splits, kps;
+    float* partial;
 };
 
 // position `item` of the flat order -> tile: XCD x (workgroups x, x + 8, ...) owns a contiguous run of the band order (bands of
 // group_m tile rows, column-major inside a band), as csrc/gemm.hip's locate_tile
-__device__ __forceinline__ void ps_locate(const PsArgs& g, int item, int& tile_m, int& tile_n) {
-    const int items = g.tiles_m * g.tiles_n;
+// (AF32 with k-splits: the flat order is split-major, so an XCD's run covers one k range)
+template <bool AF32 = false>
+__device__ __forceinline__ void ps_locate(const PsArgs& g, int item, int& tile_m, int& tile_n, int& split) {
+    const int ntiles = g.tiles_m * g.tiles_n, items = AF32 ? ntiles * g.splits : ntiles;
     const int q = items / 8, r = items % 8, xcd = item % 8, idx = item / 8;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    split = 0;
+    if constexpr (AF32) { split = bid / ntiles; bid -= split * ntiles; }
     const int gm = g.group_m > 0 ? g.group_m : 1;
     const int band = bid / (gm * g.tiles_n), within = bid - band * (gm * g.tiles_n);
     const int band_rows = min(gm, g.tiles_m - band * gm);
@@ -204,15 +213,26 @@ __device__ long long g_ps_stamp[1024 * 8 * 8];
 #define PS_STAMP(ph) do { } while (0)
 #endif
 
-template <bool CONV>
+// AF32: the "mixed" form of the backward dX products (dX = dU . W^T, include/ams.h: ams_gemm_ps_a_f32).  B is a PS32 image by LDS-DMA as
+// above; A is f32 whose bound is only known once the kernel that wrote it has finished, so it is cut HERE -- the 128-row side of the tile,
+// a third of the elements the in-product form cuts per k-tile.  Thread (row tid / 4, 8-k group tid % 4) fetches 32 bytes of a k-tile with
+// two asm buffer loads into VGPRs (hipcc does not count them: one compiler-visible VMEM load brings back a vmcnt(0) in front of every
+// LDS read of the loop), one k-tile ahead, and writes the fp16 hi / lo pieces into the SAME swizzled 128-byte rows the DMA writes (piece
+// p of row r at slot p ^ ((r >> 1) & 7)): fragment reads and the MFMA stream are those of the image form.  Per k-tile t of a workgroup:
+//        vmcnt(4) (B of t and A of t + 1 landed, B of t + 1 in flight) -> barrier -> MFMAs on t; between the groups: cut A(t + 1) into
+//        its stage, load A(t + 2) into the freed registers, DMA B(t + 2)
+// The stage A(t + 1) goes to was last read at k-tile t - 2, which every wave left before the barrier of t - 1.  Rows past M: offset
+// beyond num_records (zeros); k past the split's end: masked in the cut (a row's tail may hold its neighbour's values when lda > K).
+template <bool CONV, bool AF32 = false>
 __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
+    static_assert(!(CONV && AF32), "one A operand form per instance");
     extern __shared__ __attribute__((aligned(1024))) unsigned char ps_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int l31 = lane & 31, lk = lane >> 5;
-    const int nk = (g.K + PS_BK - 1) / PS_BK;
-    const int n_items = g.tiles_m * g.tiles_n, G = (int)gridDim.x;
+    int nk = (g.K + PS_BK - 1) / PS_BK;
+    const int n_items = g.tiles_m * g.tiles_n * (AF32 ? g.splits : 1), G = (int)gridDim.x;
     const int n_work = (n_items - (int)blockIdx.x + G - 1) / G;
     if (n_work <= 0) return;
     __builtin_amdgcn_s_setprio(2);
@@ -225,7 +245,8 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         r.z = __builtin_amdgcn_readfirstlane(r.z); r.w = __builtin_amdgcn_readfirstlane(r.w);
         return r;
     };
-    const i32x4_t rsA = rsrc(g.A, CONV ? g.a_bytes : (long)g.M * g.pitch_a), rsB = rsrc(g.B, (long)g.N * g.pitch_b);
+    const i32x4_t rsA = AF32 ? rsrc(reinterpret_cast<const unsigned char*>(g.Af), (long)g.M * g.lda * 4)
+                             : rsrc(g.A, CONV ? g.a_bytes : (long)g.M * g.pitch_a), rsB = rsrc(g.B, (long)g.N * g.pitch_b);
     const i32x4_t rsBias = rsrc(reinterpret_cast<const unsigned char*>(g.bias), g.bias ? (long)g.N * 4 : 0);       // no bias: every load out of range = 0
 
     // DMA roles: one wave-wide 16-byte piece load = 8 rows x 128 B.  Wave w moves A rows 16 w .. 16 w + 15 (2 loads) and B rows
@@ -250,11 +271,21 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
 
     const float sc_inv = (1.0f / ps_scale(g.amax_a[0])) * (1.0f / ps_scale(g.amax_b[0]));
 
-    int tile_m, tile_n, m0, n0;
+    int tile_m, tile_n, m0, n0, split = 0, kt0 = 0, kend = g.K;
+    // AF32 cut roles: row ar of the tile, k group ag (8 values), its pieces' slot XOR af; avoff = byte offset of its row (rows past M:
+    // beyond num_records, with room for the k offset below 2^32)
+    const int ar = tid >> 2, ag = tid & 3, af = (ar >> 1) & 7;
+    unsigned avoff = 0;
+    f32x4 ra0 = {}, ra1 = {};
     auto setup = [&](int i) {
-        ps_locate(g, (int)blockIdx.x + i * G, tile_m, tile_n);
+        ps_locate<AF32>(g, (int)blockIdx.x + i * G, tile_m, tile_n, split);
         m0 = tile_m * PS_BM; n0 = tile_n * PS_BN;
-        if constexpr (CONV) {
+        if constexpr (AF32) {
+            kt0 = split * (g.kps / PS_BK);
+            kend = min(g.K, (split + 1) * g.kps);
+            nk = (kend - kt0 * PS_BK + PS_BK - 1) / PS_BK;
+            avoff = (m0 + ar < g.M) ? (unsigned)((long)(m0 + ar) * g.lda * 4) + (unsigned)ag * 32u : 0x80000000u;
+        } else if constexpr (CONV) {
             // The eight LDS rows 8 A + d (d = 0 .. 7) one piece load fills hold the tile rows 64 h + 8 d + a (A = 8 h + a): positions
             // 8 apart, i.e. CONSECUTIVE pieces (p >> 3) of ONE copy (p & 7 = a; L % 128 == 0: a tile's rows are one signal's) -- the load
             // reads ~350 contiguous bytes instead of eight 128-byte runs in eight copies.  LDS piece slot ^ (A & 7) of the row's k-tile
@@ -284,7 +315,7 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         const bool isA = q < 2;
         const unsigned ld = lds0 + (unsigned)(stage * PS_STAGE + (isA ? (2 * wave + q) * 1024 : PS_A_BYTES + (4 * wave + q - 2) * 1024));
         const unsigned vo = isA ? voffA[q] : voffB[q - 2];
-        const int ko = kt * 128;                                    // (CONV: a k-tile of a row is 4 (hi, lo) piece pairs: 128 bytes as well)
+        const int ko = (kt0 + kt) * 128;                            // (CONV: a k-tile of a row is 4 (hi, lo) piece pairs: 128 bytes as well)
         unsigned keep;
         if (isA)
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
@@ -295,14 +326,39 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
     };
     auto issue = [&](int kt, int stage) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) issue1(kt, stage, q);
+        for (int q = AF32 ? 2 : 0; q < 6; ++q) issue1(kt, stage, q);
+    };
+    // AF32: the 32 bytes of A this thread cuts from k-tile kt (of the split), into ra0 / ra1; completion counted by hand (the waits name
+    // ra0 / ra1 as operands, so nothing reads them before)
+    auto load_a = [&](int kt) {
+        const unsigned vo = avoff + (unsigned)((kt0 + kt) * 128);
+        asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %2, %3, 0 offen\n\tbuffer_load_dwordx4 %1, %2, %3, 0 offen offset:16"
+                     : "=&v"(ra0), "=&v"(ra1) : "v"(vo), "s"(rsA) : "memory");
+    };
+    // ... and its fp16x3 cut (the rule of ps_pack_rows_kernel) into the stage of that k-tile
+    const float sc_a = AF32 ? ps_scale(g.amax_a[0]) : 1.0f;
+    auto cut_a = [&](int kt, int stage) {
+        float v[8] = {ra0[0], ra0[1], ra0[2], ra0[3], ra1[0], ra1[1], ra1[2], ra1[3]};
+        const int kb = (kt0 + kt) * PS_BK;
+        if (kb + PS_BK > kend) {                                    // (workgroup-uniform: the split's last k-tile)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (kb + ag * 8 + j < kend) ? v[j] : 0.f;
+        }
+        uint4 hi, lo;
+        ps_split2(v[0] * sc_a, v[1] * sc_a, hi.x, lo.x);
+        ps_split2(v[2] * sc_a, v[3] * sc_a, hi.y, lo.y);
+        ps_split2(v[4] * sc_a, v[5] * sc_a, hi.z, lo.z);
+        ps_split2(v[6] * sc_a, v[7] * sc_a, hi.w, lo.w);
+        unsigned char* const p = ps_smem + stage * PS_STAGE + ar * 128;
+        *reinterpret_cast<uint4*>(p + ((ag ^ af) * 16)) = hi;
+        *reinterpret_cast<uint4*>(p + (((4 + ag) ^ af) * 16)) = lo;
     };
 
     // the tile's 256 bias values travel the same way (wave 0, one load, slot `par` of two): older than the loads of k-tile 1, so the
     // main loop's first vmcnt(6) covers it; a plain global load here would be the one VMEM operation hipcc counts, and it then waits
     // vmcnt(0) in front of every LDS read of the loop
     auto issue_bias = [&](int par) {
-        if (wave == 0) {
+        if (!AF32 && wave == 0) {
             const unsigned lb = lds0 + (unsigned)(PS_BIAS_OFF + par * 1024);
             const unsigned vo = (unsigned)(n0 * 4 + lane * 16);
             unsigned keep;
@@ -343,8 +399,9 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         __builtin_amdgcn_s_sleep(AMS_PS_SLEEP);
 #endif
     };
-    auto mfma_tile = [&](int stage, auto PRE, int kt2, int stage2) {
-        constexpr bool pre = decltype(PRE)::value;
+    // AF32: CUT = cut A of k-tile kt2 - 1 (loaded one k-tile ago) into stage `stage_c`; PRE also loads A of kt2
+    auto mfma_tile = [&](int stage, auto PRE, int kt2, int stage2, auto CUT, int stage_c) {
+        constexpr bool pre = decltype(PRE)::value, cut = decltype(CUT)::value;
         const unsigned char* const sb = ps_smem + stage * PS_STAGE;
         f16x8_t a0[2][2], b0[2][2], a1[2][2], b1[2][2];
         if constexpr (CONV) {
@@ -360,12 +417,15 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         __builtin_amdgcn_sched_barrier(0);
         four(accs, a0, b0, 1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (pre) issue1(kt2, stage2, 0);
+        if constexpr (AF32) {
+            if constexpr (cut) cut_a(kt2 - 1, stage_c);
+            if constexpr (pre) load_a(kt2);
+        } else if constexpr (pre) issue1(kt2, stage2, 0);
         frags(sb, 1, a1, b1);
         __builtin_amdgcn_sched_barrier(0);
         four(accs, a0, b0, 0, 1);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (pre) issue1(kt2, stage2, 1);
+        if constexpr (pre && !AF32) issue1(kt2, stage2, 1);
         __builtin_amdgcn_sched_barrier(0);
         four(acc, a0, b0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -386,10 +446,21 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         }
     };
 
+    // AF32 prologue of an item: A of k-tile 0 loaded and cut in line, B of k-tile 0, then A and B of k-tile 1 in flight
+    auto start_af32 = [&]() {
+        load_a(0);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+        cut_a(0, 0);
+        issue(0, 0);
+        if (nk > 1) { load_a(1); issue(1, 1); }
+    };
     setup(0);
-    issue(0, 0);
-    issue_bias(0);
-    if (nk > 1) issue(1, 1);
+    if constexpr (AF32) start_af32();
+    else {
+        issue(0, 0);
+        issue_bias(0);
+        if (nk > 1) issue(1, 1);
+    }
     for (int wi = 0; wi < n_work; ++wi) {
         PS_STAMP(0);
 #pragma unroll
@@ -403,27 +474,32 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         for (int kt = 0; kt < nk - 2; ++kt) {
             // this wave's six loads of tile kt are older than the six of tile kt + 1: vmcnt(6) retires them (and everything older: the
             // previous tile's stores); the barrier then says every wave's pieces of tile kt are in LDS and tile kt - 1 has been read
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            // (AF32: A of kt + 1, 2 loads, then B of kt + 1, 4 DMAs, went out last: vmcnt(4) retires A of kt + 1 as well; lgkmcnt(0): the
+            // cut of A(kt) is in LDS before the barrier)
+            if constexpr (AF32) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            mfma_tile(st, std::true_type{}, kt + 2, st == 0 ? 2 : st - 1);
+            mfma_tile(st, std::true_type{}, kt + 2, st == 0 ? 2 : st - 1, std::true_type{}, st == 2 ? 0 : st + 1);
             st = st == 2 ? 0 : st + 1;
         }
         if (nk >= 2) {
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if constexpr (AF32) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            mfma_tile(st, std::false_type{}, 0, 0);
+            mfma_tile(st, std::false_type{}, nk, 0, std::true_type{}, st == 2 ? 0 : st + 1);
             st = st == 2 ? 0 : st + 1;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (AF32) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        mfma_tile(st, std::false_type{}, 0, 0);
+        mfma_tile(st, std::false_type{}, 0, 0, std::false_type{}, 0);
         PS_STAMP(1);
         // what the stores need, before the per-tile state moves on
         const int em0 = m0, en0 = n0;
         const bool more = wi + 1 < n_work;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                   // every wave has read its last fragments: all three stages are free
-        if (more) {
+        if (more && !AF32) {
             setup(wi + 1);
             issue(0, 0);                                // the next tile's first k-tile is in flight before this tile's stores
             issue_bias((wi + 1) & 1);
@@ -473,7 +549,10 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         const int rr = lane >> 4, c4 = (lane & 15) * 4;
         const int col = en0 + wn * 64 + c4;
         const bool cok = col < g.N;
-        const float4 bv = *reinterpret_cast<const float4*>(ps_smem + PS_BIAS_OFF + (wi & 1) * 1024 + (wn * 64 + c4) * 4);
+        const float4 bv = AF32 ? float4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const float4*>(ps_smem + PS_BIAS_OFF + (wi & 1) * 1024 + (wn * 64 + c4) * 4);
+        // AF32 with k-splits: this split's slab (splitk_reduce in csrc/gemm.hip adds the slabs in split order)
+        float* const out = (AF32 && g.splits > 1) ? g.partial + (long)split * g.M * g.N : g.C;
+        const long ldo = (AF32 && g.splits > 1) ? (long)g.N : g.ldc;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -488,8 +567,8 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
                 float4 v = *reinterpret_cast<const float4*>(wl + rl * 64 + c4);
                 const int row = em0 + (wm * 2 + i) * 32 + rl;
                 if (row < g.M && cok) {
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                    *reinterpret_cast<float4*>(g.C + (long)row * g.ldc + col) = v;
+                    if constexpr (!AF32) { v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w; }
+                    *reinterpret_cast<float4*>(out + (long)row * ldo + col) = v;
                 }
             }
         }
@@ -497,7 +576,8 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
         if (more) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();               // the patches have been read: stage 1 may be filled
-            if (nk > 1) issue(1, 1);
+            if constexpr (AF32) { setup(wi + 1); start_af32(); }
+            else if (nk > 1) issue(1, 1);
         }
     }
 }
@@ -552,6 +632,39 @@ ams_status ams_gemm_ps(int M, int N, int K, const void* A_img, const void* B_img
     if (grid >= 8) grid -= grid % 8;                    // a workgroup's items stay on one XCD (ps_locate)
     hipLaunchKernelGGL(gemm_ps_kernel<false>, dim3((unsigned)grid), dim3(PS_NT), PS_LDS, (hipStream_t)stream, g);
     return ams_check_launch();
+}
+
+size_t ams_gemm_ps_a_workspace_bytes(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    int kps = 0;
+    const int splits = ams_detail::dx_splits(M, N, K, ~(size_t)0, &kps);
+    return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
+}
+
+ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, const void* B_img, float* C, long ldc, const float* amax_a,
+                             const float* amax_b, void* ws, size_t ws_bytes, void* stream) {
+    AMS_REQUIRE(A && B_img && C && amax_a && amax_b && M > 0 && N > 0 && K > 0 && lda >= K);
+    AMS_REQUIRE(N % 4 == 0 && ldc % 4 == 0 && ldc >= N && lda % 4 == 0 &&
+                ((((uintptr_t)C) | ((uintptr_t)A) | ((uintptr_t)B_img) | ((uintptr_t)ws)) & 15) == 0);
+    PsArgs g{};
+    g.Af = A; g.lda = lda; g.B = (const unsigned char*)B_img; g.C = C; g.bias = nullptr; g.amax_a = amax_a; g.amax_b = amax_b;
+    g.M = M; g.N = N; g.K = K; g.ldc = ldc;
+    g.pitch_b = (unsigned)ams_ps_image_pitch(K);
+    AMS_REQUIRE((long)M * lda * 4 < (1L << 31) && (long)N * g.pitch_b < (1L << 31));            // 32-bit buffer offsets
+    g.splits = ams_detail::dx_splits(M, N, K, ws ? ws_bytes : 0, &g.kps);
+    g.partial = (float*)ws;
+    g.tiles_m = (M + PS_BM - 1) / PS_BM; g.tiles_n = (N + PS_BN - 1) / PS_BN;
+    g.group_m = ps_group_m(g.tiles_m, g.tiles_n);
+    static const int cus = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256; return n; }();
+    static const bool raised = [] { return hipFuncSetAttribute((const void*)gemm_ps_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS) == hipSuccess; }();
+    if (!raised) return AMS_E_LAUNCH_FAILED;
+    const int items = g.tiles_m * g.tiles_n * g.splits;
+    int grid = items < cus ? items : cus;
+    if (grid >= 8) grid -= grid % 8;
+    hipLaunchKernelGGL((gemm_ps_kernel<false, true>), dim3((unsigned)grid), dim3(PS_NT), PS_LDS, (hipStream_t)stream, g);
+    ams_status r = ams_check_launch();
+    if (r == AMS_OK && g.splits > 1) r = ams_detail::splitk_reduce(g.partial, C, M, N, ldc, g.splits, (hipStream_t)stream);
+    return r;
 }
 
 }  // extern "C"

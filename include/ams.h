@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 5
+#define AMS_ABI_VERSION 6
 
 typedef int32_t ams_status;
 #define AMS_OK 0
@@ -151,6 +151,17 @@ ams_status ams_ps_pack_rows(const float* x, long ldx, void* img, int R, int K, c
 ams_status ams_ps_pack_cols(const float* w, long ldw, void* img, int K, int N, const float* amax, void* stream);
 ams_status ams_gemm_ps(int M, int N, int K, const void* A_img, const void* B_img, float* C, long ldc, const float* bias,
                        const float* amax_a, const float* amax_b, void* stream);
+/* ams_gemm_ps_a_f32 (ABI 6): C[M,N] = A[M,K] . B[N,K]^T with A f32 (row pitch lda floats) and B a PS32 image -- the backward input-
+ * gradient products dX = dU . W^T, W stored [Din, Dout] row-major, whose B image is ams_ps_pack_rows(W) (no transpose) and cut before
+ * the step's product, while dU's bound only exists once the kernel that wrote it has run: A is cut inside the kernel (the 128-row side of
+ * the tile).  K is split as ams_gemm_f32's fp16x3 form splits the same product on its 128 x 256 tile; the partial slabs go to ws
+ * (ams_gemm_ps_a_workspace_bytes(M, N, K); NULL / too small = fewer splits) and are added in split order -- the same terms, MFMA order,
+ * accumulator sets, partition and reduce order, so the result is that of ams_gemm_f32 with the same bounds.  K >= 1, lda >= K,
+ * lda, N, ldc multiples of 4; A, B_img, C, ws 16-byte aligned; M * lda * 4 and the image below 2 GB.  Replaces: the gradients of
+ * utils/ops.py:366-383 (dynamic_rnn input projection: dX through [Wx_f | Wx_b]) and :501-503 (conv1d k = 1: dX). */
+size_t ams_gemm_ps_a_workspace_bytes(int M, int N, int K);
+ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, const void* B_img, float* C, long ldc, const float* amax_a,
+                             const float* amax_b, void* ws, size_t ws_bytes, void* stream);
 
 /* C[M,N] (+)= A^T . B with A stored [K, M] and B [K, N], AND bsum_out[N] (+)= column sums of B in the same pass over B: the
  * weight and bias gradients of Conv1D (utils/ops.py:501-503) and of a BLSTM layer's input kernels from one read of dY / dZ.  M, N, lda,
