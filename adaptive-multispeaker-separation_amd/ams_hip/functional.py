@@ -324,6 +324,51 @@ class Dense(Function):
         return dx, dW, db
 
 
+class DilatedStack(Function):
+    """Separator.dilated (models/network.py:528-551): x [B,T,F] -> 13 x conv2d + bias + ReLU (NHWC, C = 1 in) -> [B,T,F*cout].
+    params = (w_1, b_1, ..., w_L, b_L), w_l HWIO [kh,kw,cin,cout]; rates[l] = (rt, rf).  Saves the weights, the post-ReLU
+    outputs (the ReLU mask of a layer is y > 0) and the bounds their launches folded, nothing else; the backward runs, per layer
+    from the top, dW/db from (input, dY') and dX already masked by the layer below, so that it is that layer's dY'."""
+
+    @staticmethod
+    def forward(ctx, x, rates, *params):
+        B, T, Fq = x.shape
+        h, ah = x.reshape(B, T, Fq, 1), None           # the stack's input is data: its products run without bounds (bf16x6)
+        ys, ays = [], []
+        for l, rate in enumerate(rates):
+            w, b = params[2 * l], params[2 * l + 1]
+            aw = ops.param_amax(w) if ah is not None else None
+            h, ah = ops.dilated_conv2d_fwd(h, w, b, rate, amax=(ah, aw) if aw is not None else None)
+            ys.append(h)
+            ays.append(ah)
+        ctx.save_for_backward(x, *params[0::2], *ys)         # weights too: an in-place write before the backward is caught
+        ctx.rates, ctx.ays = rates, ays
+        out = h.view(B, T, Fq * h.shape[3])
+        return ops.tag_amax(out, ays[-1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        rates, ays = ctx.rates, ctx.ays
+        L = len(rates)
+        x, ws, ys = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + L], ctx.saved_tensors[1 + L:]
+        B, T, Fq = x.shape
+        dy, ady = ops.dilated_relu_bwd(_c(dout), ys[-1].view(dout.shape))          # the top layer's own ReLU
+        dy = dy.view(ys[-1].shape)
+        grads = [None] * (2 * L)
+        for l in range(L - 1, -1, -1):
+            w = ws[l]
+            x_l = ys[l - 1] if l > 0 else x.reshape(B, T, Fq, 1)
+            ax = ays[l - 1] if l > 0 else None
+            if ctx.needs_input_grad[2 + 2 * l] or ctx.needs_input_grad[3 + 2 * l]:
+                am = (ax, ady) if (ops.F16X3 and ax is not None) else None
+                grads[2 * l], grads[2 * l + 1] = ops.dilated_conv2d_bwd_filter(x_l, dy, w, rates[l], amax=am)
+            if l == 0 or not any(ctx.needs_input_grad[2:2 + 2 * l]):
+                break                                   # nothing below wants a gradient (the input is data)
+            aw = ops.param_amax(w) if ops.F16X3 else None
+            dy, ady = ops.dilated_conv2d_bwd_data(dy, w, ys[l - 1], rates[l], amax=(ady, aw) if aw is not None else None)
+        return (None, None) + tuple(grads)
+
+
 class L2Norm(Function):
     """tf.nn.l2_normalize over the trailing E (utils/ops.py:323-324).  Input [..., F*E] -> output [..., F, E]."""
 
@@ -450,6 +495,10 @@ def blstm(x, Kf, bf, Kb, bb, last_capped=False):
 
 def dense(x, W, b):
     return Dense.apply(_c(x), W, b)
+
+
+def dilated_stack(x, rates, params):
+    return DilatedStack.apply(_c(x), tuple(tuple(r) for r in rates), *params)
 
 
 def l2norm(u, E):

@@ -1859,3 +1859,71 @@ def kmeans_run(xn, init_idx, C, tries, iterations, beta=None, w=None, assign_at_
         idx = (best.long() + torch.arange(b, device=dev) * tries)
         out = (labels if hard else soft)[idx]
     return sel, out, best, trace
+
+
+# ------------------------------------------------------------------ dilated 2-D conv stack (csrc/conv2d.hip, network.py:528-551)
+def _conv_args(x4, w, rate):
+    B, T, F_, C = x4.shape
+    kh, kw, cin, cout = w.shape
+    if C != cin:
+        raise AmsError('dilated_conv2d: input has %d channels, the weights expect %d' % (C, cin))
+    return B, T, F_, cin, cout, kh, kw, int(rate[0]), int(rate[1])
+
+
+def _conv_ws(g, like):
+    B, T, F_, cin, cout, kh, kw = g[:7]
+    nb = load().ams_dilated_conv2d_workspace_bytes(B, T, F_, cin, cout, kh, kw)
+    if nb == 0:
+        raise AmsError('dilated_conv2d: unsupported geometry %r' % (g,))
+    return _ws(nb, like), nb
+
+
+def dilated_conv2d_fwd(x4, w, b, rate, amax=None, want_amax=True):
+    """y [B,T,F,cout] = relu(conv2d(x4 [B,T,F,cin], w [kh,kw,cin,cout], dilation rate, SAME) + b) and, want_amax, max |y| (1 element,
+    folded by the launch).  amax = (bound of x4, bound of w): fp16x3 products."""
+    _chk(x4, w, b)
+    g = _conv_args(x4, w, rate)
+    y = torch.empty(g[:3] + (g[4],), dtype=torch.float32, device=x4.device)
+    ay = torch.empty(1, dtype=torch.float32, device=x4.device) if want_amax else None
+    pa, pb, _ = _bounds(amax)
+    check(load().ams_dilated_conv2d_fwd(_p(x4), _p(w), _p(b), _p(y), *g, pa, pb, _p(ay), _vp(0), 0, _s()), 'ams_dilated_conv2d_fwd')
+    return y, ay
+
+
+def dilated_conv2d_bwd_data(dy4, w, y_below, rate, amax=None, want_amax=True):
+    """dx [B,T,F,cin] = conv2d^T(dy4, w) * (y_below > 0): the gradient of the pre-ReLU sum of the layer below, and max |dx|.
+    amax = (bound of dy4, bound of w)."""
+    _chk(dy4, w, y_below)
+    kh, kw, cin, cout = w.shape
+    B, T, F_, _ = dy4.shape
+    g = (B, T, F_, cin, cout, kh, kw, int(rate[0]), int(rate[1]))
+    dx = torch.empty((B, T, F_, cin), dtype=torch.float32, device=dy4.device)
+    adx = torch.empty(1, dtype=torch.float32, device=dy4.device) if want_amax else None
+    ws, nb = _conv_ws(g, dy4)
+    pa, pb, _ = _bounds(amax)
+    check(load().ams_dilated_conv2d_bwd_data(_p(dy4), _p(w), _p(y_below), _p(dx), *g, pa, pb, _p(adx), _p(ws), nb, _s()),
+          'ams_dilated_conv2d_bwd_data')
+    return dx, adx
+
+
+def dilated_conv2d_bwd_filter(x4, dy4, w, rate, amax=None):
+    """(dw [kh,kw,cin,cout], db [cout]) of one layer from its input x4 and the gradient dy4 of its pre-ReLU sum.
+    amax = (bound of x4, bound of dy4)."""
+    _chk(x4, dy4)
+    g = _conv_args(x4, w, rate)
+    dw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x4.device)
+    db = torch.empty(w.shape[3], dtype=torch.float32, device=x4.device)
+    ws, nb = _conv_ws(g, x4)
+    pa, pb, _ = _bounds(amax)
+    check(load().ams_dilated_conv2d_bwd_filter(_p(x4), _p(dy4), _p(dw), _p(db), *g, pa, pb, _p(ws), nb, _s()),
+          'ams_dilated_conv2d_bwd_filter')
+    return dw, db
+
+
+def dilated_relu_bwd(dy, y, want_amax=True):
+    """dx = dy * (y > 0) and max |dx|: the top layer's own ReLU."""
+    _chk(dy, y)
+    dx = torch.empty_like(dy)
+    adx = torch.empty(1, dtype=torch.float32, device=dy.device) if want_amax else None
+    check(load().ams_dilated_conv2d_relu_bwd(_p(dy), _p(y), _p(dx), dy.numel(), _p(adx), _s()), 'ams_dilated_conv2d_relu_bwd')
+    return dx, adx

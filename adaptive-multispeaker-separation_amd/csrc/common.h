@@ -36,6 +36,13 @@ ams_status conv_maxpool_ps(const float* x, const float* f, float* pmax, int32_t*
 // product (cost model, k per split in *kps) and the slab reduce it runs -- the same partition and summation order, so the same bits
 int dx_splits(int M, int N, int K, size_t ws_bytes, int* kps);
 ams_status splitk_reduce(const float* partial, float* C, int M, int N, long ldc, int splits, hipStream_t st);
+// csrc/gemm.hip, used by csrc/conv2d.hip: the dilated conv2d products as implicit GEMMs (A_CONV / A_CONV_T loaders)
+ams_status conv_fwd_or_dx(const float* x, const float* w, const float* bias, float* y, int M, int N, int T, int F, int lc, int kh, int kw,
+                          int rt, int rf, int relu, const float* emask, const float* amax_a, const float* amax_b, float* amax_out,
+                          hipStream_t st);
+ams_status conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* bsum_ws, int P, int N, int T, int F, int lc, int kh,
+                      int kw, int rt, int rf, const float* amax_a, const float* amax_b, void* ws, size_t ws_bytes, hipStream_t st);
+size_t conv_wgrad_ws_bytes(int P, int N, int Mrows);
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -6,6 +6,8 @@
 //   A_FRAMES A[m,k] = x[b*L + t*hop + k - pl], m = b*T+t (adaptive analysis filterbank = strided conv;
 //                                                         reference models/adapt.py:122)
 //   A_FRAMES_T  A[m=k_w, k=(b,t)] = frame element        (filter gradient of the same conv)
+//   A_CONV   A[m=pixel, k=(tap,c)] = x[pixel + off(tap), c], 0 outside the image   (dilated conv2d, implicit GEMM: csrc/conv2d.hip)
+//   A_CONV_T A[m=(tap,c), k=pixel] = the same element                            (its weight gradient)
 // and B-operand loaders B_ROW (B[k*ldb+n]) / B_COL (B[n*ldb+k]).
 //
 // Tiling: 128x128x8 block tile (BK = 8 measured best: 16.8 KB LDS and 95 VGPRs give 5 waves/SIMD, +4..10 % over BK = 16), 256 threads = 4 waves in 2x2, each wave 64x64 = 2x2 MFMA 32x32 tiles
@@ -92,7 +94,7 @@ constexpr int X6_BK = 32;           // k-tile of the bf16x6 kernel
 constexpr int PAD_T = 2;   // k-contiguous source, transposed scalar LDS writes: stride 130 -> conflict-free
 constexpr int PAD_V = 4;   // m/n-contiguous source, float4 LDS writes: stride 132 keeps 16B alignment
 
-enum { A_ROW = 0, A_COL = 1, A_FRAMES = 2, A_FRAMES_T = 3 };
+enum { A_ROW = 0, A_COL = 1, A_FRAMES = 2, A_FRAMES_T = 3, A_CONV = 4, A_CONV_T = 5 };
 enum { B_ROW = 0, B_COL = 1 };
 enum { EPI_STORE = 0, EPI_MAXPOOL = 1 };
 
@@ -131,7 +133,27 @@ struct GemmArgs {
     int c_vec;                 // C (and the partial slabs, bias) are 16-byte addressable along n: the x6 epilogue stores rows as float4 through LDS
     int amax_fold;             // amax_out is folded inside the launch through sk_flags[512 ..] (else: atomicMax on a word the entry point cleared)
     unsigned* amax_out;        // != NULL: atomicMax of the bit patterns of |C| as stored (one atomic per workgroup and tile)
+    // A_CONV / A_CONV_T: NHWC activations [B, T, F, C = 2^cv_lc]; tap (i, j) of a [cv_kh, cv_kw] kernel reads the pixel at
+    // ((i - (kh-1)/2) cv_rt, (j - (kw-1)/2) cv_rf) (negative rates: the mirrored taps of the input gradient)
+    int cv_T, cv_F, cv_lc, cv_kh, cv_kw, cv_rt, cv_rf;
+    // epilogue (splits == 1 only): relu -> max(c, 0); emask != NULL -> c * (emask[row * ldc + col] > 0)
+    int relu; const float* emask;
 };
+
+// A_CONV / A_CONV_T: address of the 4 channels c..c+3 of tap `tap` around pixel p (row of the image), and whether it is inside
+__device__ __forceinline__ const float* conv_src(const GemmArgs& g, long p, int t, int f, int tap, int c, bool& ok) {
+    const int i = tap / g.cv_kw, j = tap - i * g.cv_kw;
+    const int dt = (i - (g.cv_kh - 1) / 2) * g.cv_rt, df = (j - (g.cv_kw - 1) / 2) * g.cv_rf;
+    const int t2 = t + dt, f2 = f + df;
+    ok = t2 >= 0 && t2 < g.cv_T && f2 >= 0 && f2 < g.cv_F;
+    const long q = ok ? p + (long)dt * g.cv_F + df : p;
+    return g.A + (q << g.cv_lc) + c;
+}
+// pixel p -> packed (t << 16 | f)
+__device__ __forceinline__ int conv_tf(const GemmArgs& g, long p) {
+    const long bt = p / g.cv_F;
+    return (int)((bt % g.cv_T) << 16) | (int)(p - bt * g.cv_F);
+}
 
 template <int AMODE>
 __device__ __forceinline__ float loadA1(const GemmArgs& g, int m, int k) {
@@ -145,6 +167,14 @@ __device__ __forceinline__ float loadA1(const GemmArgs& g, int m, int k) {
         int b = m / g.fr_T, t = m - b * g.fr_T;
         int p = t * g.fr_hop + k - g.fr_pl;
         return (p >= 0 && p < g.fr_L) ? g.A[(long)b * g.fr_L + p] : 0.f;
+    }
+    if (AMODE == A_CONV || AMODE == A_CONV_T) {
+        const long p = AMODE == A_CONV ? m : k;
+        const int kk = AMODE == A_CONV ? k : m;
+        const int tf = conv_tf(g, p);
+        bool ok;
+        const float* src = conv_src(g, p, tf >> 16, tf & 0xffff, kk >> g.cv_lc, kk & ((1 << g.cv_lc) - 1), ok);
+        return ok ? *src : 0.f;
     }
     // A_FRAMES_T: m = filter tap, k = frame index (b,t)
     int b = k / g.fr_T, t = k - b * g.fr_T;
@@ -241,6 +271,8 @@ __device__ __forceinline__ void store_tile(const GemmArgs& g, const f32x16 (&acc
                     float v = acc[i][j][r] + bv;
                     float* p = out + (long)row * ldo + col;
                     if (g.splits == 1 && g.accumulate) v += *p;
+                    if (g.relu) v = v > 0.f ? v : 0.f;
+                    if (g.emask) v = g.emask[(long)row * ldo + col] > 0.f ? v : 0.f;
                     *p = v;
                 }
             }
@@ -285,7 +317,7 @@ __device__ __forceinline__ void maxpool_epilogue(const GemmArgs& g, const f32x16
 }
 
 // Is operand A contiguous along k (-> transposed LDS writes) ?
-template <int AMODE> struct AKContig { static constexpr bool v = (AMODE == A_ROW || AMODE == A_FRAMES); };
+template <int AMODE> struct AKContig { static constexpr bool v = (AMODE == A_ROW || AMODE == A_FRAMES || AMODE == A_CONV); };
 
 
 #ifndef AMS_GEMM_WPE
@@ -357,6 +389,13 @@ __global__ __launch_bounds__(256, AMS_GEMM_WPE) void gemm_f32_kernel(GemmArgs g)
 #pragma unroll
     for (int h = 0; h < NLD; ++h) arow[h] = (AMODE == A_ROW) ? (long)min(m0 + (tid + h * 256) / KQ, g.M - 1) * g.lda : 0;
     int fp0[NLD];                                   // A_FRAMES (VEC): first sample of this thread's frame, relative to its row
+    if (AMODE == A_CONV) {                          // A_CONV: the pixel of this thread's row and its (t, f)
+#pragma unroll
+        for (int h = 0; h < NLD; ++h) {
+            arow[h] = min(m0 + (tid + h * 256) / KQ, g.M - 1);
+            fp0[h] = conv_tf(g, arow[h]);
+        }
+    }
     if (AMODE == A_FRAMES) {
 #pragma unroll
         for (int h = 0; h < NLD; ++h) {
@@ -379,6 +418,12 @@ __global__ __launch_bounds__(256, AMS_GEMM_WPE) void gemm_f32_kernel(GemmArgs g)
                     const int p = fp0[h] + k;
                     va[h] = k < k_end && p >= 0 && p < g.fr_L;
                     ra[h] = *reinterpret_cast<const float4*>(g.A + arow[h] + min(max(p, 0), g.fr_L - 4));
+                } else if (AMODE == A_CONV) {           // C % 4 == 0: a float4 lies in one tap, all inside or all padding
+                    const int k = k0 + (q % KQ) * 4, kc = min(k, g.K - 4);
+                    bool ok;
+                    ra[h] = *reinterpret_cast<const float4*>(conv_src(g, arow[h], fp0[h] >> 16, fp0[h] & 0xffff, kc >> g.cv_lc,
+                                                                      kc & ((1 << g.cv_lc) - 1), ok));
+                    va[h] = k < k_end && ok;
                 } else if (AK) {                        // A_ROW: float4 along k (K % 4 == 0, so k < k_end covers all four)
                     const int k = k0 + (q % KQ) * 4;
                     va[h] = k < k_end;
@@ -390,6 +435,13 @@ __global__ __launch_bounds__(256, AMS_GEMM_WPE) void gemm_f32_kernel(GemmArgs g)
                     const int p = t * g.fr_hop + m - g.fr_pl;          // multiple of 4: inside the signal or inside the padding
                     va[h] = k < k_end && m < g.M && p >= 0 && p < g.fr_L;
                     ra[h] = *reinterpret_cast<const float4*>(g.A + (long)b * g.fr_L + min(max(p, 0), g.fr_L - 4));
+                } else if (AMODE == A_CONV_T) {         // weight gradient: m = (tap, c) (float4 along c), k = pixel
+                    const int k = k0 + (q >> 5), m = m0 + (q & 31) * 4;
+                    const long p = min(k, g.K - 1);
+                    const int tf = conv_tf(g, p), mc = min(m, g.M - 4);
+                    bool ok;
+                    ra[h] = *reinterpret_cast<const float4*>(conv_src(g, p, tf >> 16, tf & 0xffff, mc >> g.cv_lc, mc & ((1 << g.cv_lc) - 1), ok));
+                    va[h] = k < k_end && m < g.M && ok;
                 } else {                                // A_COL: float4 along m (M % 4 == 0)
                     const int k = k0 + (q >> 5), m = m0 + (q & 31) * 4;
                     va[h] = k < k_end && !(g.mask_period && (k % g.mask_period) == g.mask_skip);
@@ -415,7 +467,7 @@ __global__ __launch_bounds__(256, AMS_GEMM_WPE) void gemm_f32_kernel(GemmArgs g)
             const int q = tid + h * 256;
             if (AK) {
                 const int m = m0 + (q / KQ), k = k0 + (q % KQ) * 4;
-                bool fast = g.a_vec && m < g.M && k + 3 < k_end;
+                bool fast = g.a_vec && m < g.M && k + 3 < k_end && AMODE != A_CONV;
                 if (AMODE == A_FRAMES && fast) {
                     int b = m / g.fr_T, t = m - b * g.fr_T;
                     int p = t * g.fr_hop + k - g.fr_pl;
@@ -830,6 +882,13 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
 #pragma unroll
             for (int h = 0; h < NSA; ++h) arow[h] = (long)min(m0 + krow + (NT / 4) * h, g.M - 1) * g.lda;
         }
+        if (AMODE == A_CONV) {
+#pragma unroll
+            for (int h = 0; h < NSA; ++h) {
+                arow[h] = min(m0 + krow + (NT / 4) * h, g.M - 1);
+                fp0[h] = conv_tf(g, arow[h]);
+            }
+        }
         if (AMODE == A_FRAMES) {
 #pragma unroll
             for (int h = 0; h < NSA; ++h) {
@@ -861,6 +920,12 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                         const int p = fp0[h] + k;
                         va[2 * h + c] = k < k_end && p >= 0 && p < g.fr_L;
                         ra[2 * h + c] = *reinterpret_cast<const float4*>(g.A + arow[h] + min(max(p, 0), g.fr_L - 4));
+                    } else if (AMODE == A_CONV) {       // C % 4 == 0: a float4 lies in one tap, all inside or all padding
+                        const int kc = min(k, g.K - 4);
+                        bool ok;
+                        ra[2 * h + c] = *reinterpret_cast<const float4*>(conv_src(g, arow[h], fp0[h] >> 16, fp0[h] & 0xffff,
+                                                                                  kc >> g.cv_lc, kc & ((1 << g.cv_lc) - 1), ok));
+                        va[2 * h + c] = k < k_end && ok;
                     } else {                            // A_ROW (K % 4 == 0)
                         va[2 * h + c] = k < k_end;
                         ra[2 * h + c] = *reinterpret_cast<const float4*>(g.A + arow[h] + min(k, g.K - 4));
@@ -876,6 +941,11 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                     const int p = t * g.fr_hop + m - g.fr_pl;
                     va[r] = k < k_end && m < g.M && p >= 0 && p < g.fr_L;
                     ra[r] = *reinterpret_cast<const float4*>(g.A + (long)b * g.fr_L + min(max(p, 0), g.fr_L - 4));
+                } else if (AMODE == A_CONV_T) {         // weight gradient: m = (tap, c), k = pixel
+                    const int tf = conv_tf(g, kc), mc = min(m, g.M - 4);
+                    bool ok;
+                    ra[r] = *reinterpret_cast<const float4*>(conv_src(g, kc, tf >> 16, tf & 0xffff, mc >> g.cv_lc, mc & ((1 << g.cv_lc) - 1), ok));
+                    va[r] = k < k_end && m < g.M && ok;
                 } else {                                // A_COL (M % 4 == 0)
                     va[r] = k < k_end && !(g.mask_period && (k % g.mask_period) == g.mask_skip);
                     ra[r] = *reinterpret_cast<const float4*>(g.A + (long)kc * g.lda + min(m, g.M - 4));
@@ -1220,6 +1290,11 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
                             float4* const p = reinterpret_cast<float4*>(out + (long)row * ldo + col);
                             if (g0.splits == 1 && g0.accumulate) { const float4 o = *p; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+                            if (g0.relu) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
+                            if (g0.emask) {
+                                const float4 e = *reinterpret_cast<const float4*>(g0.emask + (long)row * ldo + col);
+                                v.x = e.x > 0.f ? v.x : 0.f; v.y = e.y > 0.f ? v.y : 0.f; v.z = e.z > 0.f ? v.z : 0.f; v.w = e.w > 0.f ? v.w : 0.f;
+                            }
                             *p = v;
                             vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
                         }
@@ -1242,6 +1317,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                             float v = acc[i][j][r] + bv;
                             float* p = out + (long)row * ldo + col;
                             if (g0.splits == 1 && g0.accumulate) v += *p;
+                            if (g0.relu) v = v > 0.f ? v : 0.f;
+                            if (g0.emask) v = g0.emask[(long)row * ldo + col] > 0.f ? v : 0.f;
                             *p = v;
                             vmax = fmaxf(vmax, fabsf(v));
                         }
@@ -1470,7 +1547,7 @@ inline SkPlan sk_plan(int tiles_all, int K, const TilePlan& tp, int wgcu) {
 template <int AMODE, int BMODE>
 ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, hipStream_t st, int nbatch = 1,
                   float* bsum_out = nullptr, int bsum_accumulate = 0, float* bsum_ws = nullptr) {
-    constexpr bool AKc = (AMODE == A_ROW), BKcc = (BMODE == B_COL);
+    constexpr bool AKc = (AMODE == A_ROW || AMODE == A_CONV), BKcc = (BMODE == B_COL);
     const int lds_pad = opt.lds_pad < 0 ? 0 : opt.lds_pad;
     const bool capped = lds_pad > 0;
     const bool vec_off = tuning().novec;
@@ -1493,7 +1570,8 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     g.group_m = choose_group_m(ceil_div(g.M, tp.bm), ceil_div(g.N, tp.bn));
     int splits = 1;
     double t_split = 1e30;
-    if (ws && !opt.amax_out) {
+    const bool whole = opt.amax_out || g.relu || g.emask;            // epilogues that need the whole k range in one workgroup
+    if (ws && !whole) {
         splits = choose_splits(g.M, g.N, g.K, nbatch, tp, &t_split);
         if (tuning().splits > 0) splits = tuning().splits;
         while (splits > 1 && (size_t)nbatch * splits * g.M * g.N * sizeof(float) > ws_bytes) --splits;
@@ -1525,6 +1603,7 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     int kps = ceil_div(g.K, splits);
     kps = ceil_div(kps, tp.bk) * tp.bk;
     splits = ceil_div(g.K, kps);
+    if (whole && splits > 1) return AMS_E_INVALID_ARG;
     g.splits = splits;
     g.k_per_split = kps;
     g.partial = (float*)ws;
@@ -1642,6 +1721,42 @@ __attribute__((visibility("hidden"))) ams_status splitk_reduce(const float* part
     hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3(blocks, 1), dim3(256), 0, st, partial, C, (const float*)nullptr, M, N, ldc, splits, 0, 0L, 0L);
     return ams_check_launch();
 }
+
+
+// The dilated conv2d products as implicit GEMMs (csrc/conv2d.hip): no im2col image; x NHWC [pixels, C = 2^lc] (C % 4 == 0).
+//   fwd_or_dx: C[M = pixels, N] = A_CONV(x, taps) . W[taps C, N] (+ bias), epilogue relu / emask (y_{l-1} > 0), amax_out = max |C|
+//   wgrad:     dW[taps C, N] = A_CONV_T(x) . dy[pixels, N], bsum_out = colsum(dy) (split-K slabs in ws, added in split order)
+__attribute__((visibility("hidden"))) ams_status conv_fwd_or_dx(const float* x, const float* w, const float* bias, float* y, int M, int N,
+                                                              int T, int F, int lc, int kh, int kw, int rt, int rf, int relu,
+                                                              const float* emask, const float* amax_a, const float* amax_b, float* amax_out,
+                                                              hipStream_t st) {
+    GemmArgs g{};
+    g.A = x; g.B = w; g.C = y; g.bias = bias;
+    g.M = M; g.N = N; g.K = kh * kw * (1 << lc); g.lda = 0; g.ldb = N; g.ldc = N;
+    g.cv_T = T; g.cv_F = F; g.cv_lc = lc; g.cv_kh = kh; g.cv_kw = kw; g.cv_rt = rt; g.cv_rf = rf;
+    g.relu = relu; g.emask = emask;
+    g.a_vec = aligned16(x) && lc >= 2;
+    g.b_vec = aligned16(w) && (N % 4 == 0);
+    LaunchOpt o; o.amax_a = amax_a; o.amax_b = amax_b;
+    const bool x6 = use_x6() && g.a_vec && g.b_vec && !tuning().novec && g.K >= 4 && N >= 4;
+    if (amax_out && x6) o.amax_out = reinterpret_cast<unsigned*>(amax_out);
+    ams_status s = launch<A_CONV, B_ROW>(g, o, nullptr, 0, st);
+    if (s == AMS_OK && amax_out && !x6) s = ams_absmax_f32(y, (long)M * N, amax_out, st);   // the f32 kernel does not measure its output
+    return s;
+}
+__attribute__((visibility("hidden"))) ams_status conv_wgrad(const float* x, const float* dy, float* dw, float* db, float* bsum_ws, int P, int N,
+                                                          int T, int F, int lc, int kh, int kw, int rt, int rf, const float* amax_a,
+                                                          const float* amax_b, void* ws, size_t ws_bytes, hipStream_t st) {
+    GemmArgs g{};
+    g.A = x; g.B = dy; g.C = dw; g.bias = nullptr;
+    g.M = kh * kw * (1 << lc); g.N = N; g.K = P; g.lda = 0; g.ldb = N; g.ldc = N;
+    g.cv_T = T; g.cv_F = F; g.cv_lc = lc; g.cv_kh = kh; g.cv_kw = kw; g.cv_rt = rt; g.cv_rf = rf;
+    g.a_vec = aligned16(x) && lc >= 2;
+    g.b_vec = aligned16(dy) && (N % 4 == 0);
+    LaunchOpt o; o.amax_a = amax_a; o.amax_b = amax_b;
+    return launch<A_CONV_T, B_ROW>(g, o, ws, ws_bytes, st, 1, db, 0, bsum_ws);
+}
+size_t conv_wgrad_ws_bytes(int P, int N, int Mrows) { return ams_gemm_workspace_bytes(Mrows, N, P, 1, 0); }
 
 }  // namespace ams_detail
 

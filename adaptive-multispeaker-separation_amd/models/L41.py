@@ -47,7 +47,7 @@ class L41Model(Separator):
         y = self.y
         self.true_masks = Node('true_masks', lambda run: 1.0 + y.value(run), register=False)
         layers = [BLSTM(self.layer_size, name='BLSTM_' + str(i), drop_val=self.rdropout,
-                        in_dim=(Fq if i == 0 else self.layer_size)) for i in range(self.nb_layers)]
+                        in_dim=(self.in_dim if i == 0 else self.layer_size)) for i in range(self.nb_layers)]
         conv = Conv1D([1, self.layer_size, E * Fq])
         x_node, normalize = self.X, self.normalize
 

@@ -22,7 +22,7 @@ class DPCL(Separator):
         self.count_labels_for = self.embedding_size          # network.py create_masks: labels are counted as they are made (fused loss)
         E, Fq = self.embedding_size, self.F
         layers = [BLSTM(self.layer_size, name='BLSTM_' + str(i), drop_val=self.rdropout,
-                        in_dim=(Fq if i == 0 else self.layer_size)) for i in range(self.nb_layers)]
+                        in_dim=(self.in_dim if i == 0 else self.layer_size)) for i in range(self.nb_layers)]
         conv = Conv1D([1, self.layer_size, E * Fq])
         x_node = self.X
 

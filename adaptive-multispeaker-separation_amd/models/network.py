@@ -18,7 +18,7 @@ from ams_hip import functional as F
 from ams_hip import ops as K
 from ams_hip.graph import Node, Placeholder, Run, get_default_graph, scope
 from ams_hip.optim import FlatOptimizer
-from utils.ops import BLSTM, Conv1D, f_props
+from utils.ops import BLSTM, Conv1D, Conv2D, conv2d_stack, f_props
 
 _ADJ = ['autumn', 'hidden', 'bitter', 'misty', 'silent', 'empty', 'dry', 'dark', 'summer', 'icy', 'quiet', 'white', 'cool',
         'spring', 'winter', 'patient', 'twilight', 'dawn', 'crimson', 'wispy', 'weathered', 'blue', 'billowing', 'broken']
@@ -681,8 +681,6 @@ class Separator(Network):
         self.ns_method = kwargs['ns_method']
 
         self.add_dilated = kwargs['add_dilated']
-        if self.add_dilated:
-            raise NotImplementedError('--add_dilated (experimental dilated front, network.py:527-551) is out of scope')
 
         self.graph = get_default_graph()
         self.plugged = plugged
@@ -729,6 +727,9 @@ class Separator(Network):
             self.window_size = kwargs['window_size']
             self.hop_size = kwargs['hop_size']
             self.F = kwargs['window_size'] // 2 + 1
+        # width of what the first BLSTM reads: the dilated stack (STFT path only; the front path ignores the flag, network.py:357-400)
+        # leaves 4 channels per frequency
+        self.in_dim = self.F * (4 if (self.add_dilated and not self.plugged) else 1)
 
     def _weight_masks(self, y, run):
         """network.py:381-396: magnitude-weighted masks / silence loss mask (off in the shipped launchers)."""
@@ -765,6 +766,8 @@ class Separator(Network):
                 def _sil(run):
                     return K.row_transform(src.value(run).contiguous(), norm='silent', thr=thr / 20.)
                 self.X = Node('silent_mask', _sil, register=False)
+            if self.add_dilated:
+                self.dilated
             self.prediction
             if self.args['model_folder'] is None:
                 self.cost_model = self.cost
@@ -820,6 +823,22 @@ class Separator(Network):
     @scope
     def prediction(self):
         pass
+
+    @scope
+    def dilated(self):
+        """network.py:527-551: 13 dilated conv2d + ReLU layers over the conditioned magnitudes X [B,T,F] (NHWC, one channel) ->
+        X [B,T,4F].  X_input, the magnitude `separate` masks, is not touched.  The reference reshapes to size_t from chunk_size, which
+        is the STFT frame count for chunk-length inputs: the actual T is used."""
+        specs = [((1, 7), (1, 1), 128), ((7, 1), (1, 1), 128)] + [((5, 5), (r, 1), 128) for r in (4, 8, 16, 32)] + \
+                [((5, 5), (r, r), 128) for r in (1, 2, 4, 8, 16, 32)] + [((5, 5), (1, 1), 4)]
+        layers, cin = [], 1
+        for i, (kernel, rate, cout) in enumerate(specs):
+            layers.append(Conv2D(cin, cout, kernel, rate, name='Conv' if i == 0 else 'Conv_%d' % i))
+            cin = cout
+        self.dilated_layers = layers
+        src = self.X
+        self.X = Node('output', lambda run: conv2d_stack(layers, src.value(run)))
+        return self.X
 
     @scope
     def separate(self):

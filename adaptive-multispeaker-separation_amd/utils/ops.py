@@ -1,6 +1,6 @@
 """Host mirror of the reference's op library subset used on the hot path (reference utils/ops.py).
 
-Same names and call shapes -- ``scope``, ``get_scope_variable``, ``f_props``, ``BLSTM``, ``Conv1D``, ``Reshape``,
+Same names and call shapes -- ``scope``, ``get_scope_variable``, ``f_props``, ``BLSTM``, ``Conv1D``, ``Conv2D``, ``Reshape``,
 ``Normalize``, ``log10``, ``kl_div`` -- but every ``f_prop`` launches hand-written HIP kernels through
 ams_hip.functional instead of building TF graph ops.  Layers create their variables at construction time
 under the active variable scope, so names match the reference's checkpoints
@@ -38,9 +38,12 @@ def _graph_rng():
 
 def xavier_uniform(shape):
     """tf.contrib.layers.xavier_initializer_conv2d for the shapes the reference uses:
-    [W] -> +-sqrt(3/W);  [W,N] -> +-sqrt(6/(W+N))."""
+    [W] -> +-sqrt(3/W);  [W,N] -> +-sqrt(6/(W+N));  conv2d HWIO [kh,kw,cin,cout] -> +-sqrt(6/(kh kw cin + kh kw cout))."""
     if len(shape) == 1:
         lim = np.sqrt(3.0 / shape[0])
+    elif len(shape) == 4:
+        rf = shape[0] * shape[1]
+        lim = np.sqrt(6.0 / (rf * shape[2] + rf * shape[3]))
     else:
         lim = np.sqrt(6.0 / (shape[0] + shape[1]))
     return _graph_rng().uniform(-lim, lim, size=shape).astype('float32')
@@ -126,3 +129,22 @@ class Conv1D:
 
     def f_prop(self, x):
         return self.function(F.dense(x, self.W, self.b))
+
+
+class Conv2D:
+    """tf.contrib.layers.conv2d(x, cout, [kh, kw], rate=[rt, rf]) with the TF 1.4 defaults the reference relies on
+    (models/network.py:531-549): stride 1, SAME, bias, ReLU; variables '<name>/weights' HWIO [kh,kw,cin,cout] (xavier_initializer,
+    uniform) and '<name>/biases' (zeros).  The layers of one stack run as ONE autograd node: see conv2d_stack."""
+
+    def __init__(self, cin, cout, kernel, rate, name='Conv'):
+        g = get_default_graph()
+        with g.variable_scope(name):
+            self.w = g.get_variable('weights', (kernel[0], kernel[1], cin, cout), xavier_uniform)
+            self.b = g.get_variable('biases', (cout,), lambda s: np.zeros(s, 'float32'))
+        self.rate = (int(rate[0]), int(rate[1]))
+        self.name = name
+
+
+def conv2d_stack(layers, x):
+    """x [B,T,F] (one input channel) through the Conv2D layers -> [B,T,F*cout] (feature index f*cout + c)."""
+    return F.dilated_stack(x, [l.rate for l in layers], [p for l in layers for p in (l.w, l.b)])

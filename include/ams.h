@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 6
+#define AMS_ABI_VERSION 7
 
 typedef int32_t ams_status;
 #define AMS_OK 0
@@ -170,6 +170,36 @@ ams_status ams_gemm_f32_at_b_colsum(int M, int N, int K, const float* A, long ld
                                     int accumulate, float* bsum_out, int bsum_accumulate, float* bsum_ws, const float* amax_a,
                                     const float* amax_b, int lds_pad, void* ws, size_t ws_bytes, void* sk_scratch, size_t sk_bytes,
                                     void* stream);
+/* ---- dilated 2-D convolution stack (ABI 7; csrc/conv2d.hip)      models/network.py:528-551 ----
+ * One tf.contrib.layers.conv2d(y, cout, [kh, kw], rate=[rt, rf]) of Separator.dilated: stride 1, SAME, bias, ReLU.  Activations NHWC
+ * [B, T, F, C] row-major (pixel p = (b T + t) F + f, channels fastest); weights HWIO [kh, kw, cin, cout]; kh, kw odd, tap (i, j) reads
+ * the pixel at ((i - (kh-1)/2) rt, (j - (kw-1)/2) rf), zero outside the image.  cout a power of two >= 4; cin == 1 (the first layer;
+ * no dX) or a power of two >= 4; T, F < 65536; B T F max(cin, cout) < 2^31.  Activations, weights, biases, gradients and ws 16-byte
+ * aligned.  ws: ams_dilated_conv2d_workspace_bytes(same B, T, F, cin, cout, kh, kw; the rates do not matter), for _bwd_data and
+ * _bwd_filter (the forward takes none: NULL, 0).  cin, cout >= 4: implicit GEMMs on the product kernel (no im2col image), in
+ * ams_gemm_f32's arithmetic classes -- fp16x3 when both bounds are given, else bf16x6 / native f32 by ams_gemm_set_arith.  cin == 1
+ * (forward) and cout == 4 (forward, dW / db): direct f32-FMA kernels, whatever the class.  Deterministic (fixed split and slab order;
+ * the folded bounds are maxima).  A folded bound drops NaN (as amax_out of the products): a NaN output shows in the output itself.
+ *   _fwd         y = relu(conv(x, w) + bias), bias + ReLU in the product's epilogue.  Reads amax_x, amax_w (optional, both or
+ *                neither).  amax_y (optional): the launch leaves max |y| there.
+ *   _bwd_data    dx = conv^T(dy, w) (mirrored taps, W^T per tap), times (y_below > 0) in the epilogue when y_below (the post-ReLU
+ *                output of the layer below) is given: dx is then the gradient of that layer's pre-ReLU sum.  Reads amax_dy, amax_w;
+ *                amax_dx (optional, needs y_below) receives max |dx|.  cin % 4 == 0.
+ *   _bwd_filter  dw [kh kw cin, cout] = sum_p x[p + off(tap), ci] dy[p, co], db [cout] = sum_p dy[p, co]; written, not accumulated.
+ *                Reads amax_x, amax_dy (cin >= 4, cout > 4).
+ *   _relu_bwd    dx[i] = dy[i] * (y[i] > 0), n % 4 == 0 (the top layer's own ReLU; dx == dy allowed); amax_dx (optional) receives
+ *                max |dx|. */
+size_t ams_dilated_conv2d_workspace_bytes(int B, int T, int F, int cin, int cout, int kh, int kw);
+ams_status ams_dilated_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int F, int cin, int cout,
+                                  int kh, int kw, int rt, int rf, const float* amax_x, const float* amax_w, float* amax_y, void* ws,
+                                  size_t ws_bytes, void* stream);
+ams_status ams_dilated_conv2d_bwd_data(const float* dy, const float* w, const float* y_below, float* dx, int B, int T, int F, int cin,
+                                       int cout, int kh, int kw, int rt, int rf, const float* amax_dy, const float* amax_w,
+                                       float* amax_dx, void* ws, size_t ws_bytes, void* stream);
+ams_status ams_dilated_conv2d_bwd_filter(const float* x, const float* dy, float* dw, float* db, int B, int T, int F, int cin,
+                                         int cout, int kh, int kw, int rt, int rf, const float* amax_x, const float* amax_dy, void* ws,
+                                         size_t ws_bytes, void* stream);
+ams_status ams_dilated_conv2d_relu_bwd(const float* dy, const float* y, float* dx, long n, float* amax_dx, void* stream);
 /* nbatch products of ONE shape in one launch; operand z lives at A + z*a_zs, B + z*b_zs, C + z*c_zs (element offsets, any
  * sign).  No bias.  Used for the two BLSTM directions' recurrent-kernel gradients (h_prev^T . dZ). */
 ams_status ams_gemm_f32_batched(int transA, int transB, int M, int N, int K, const float* A, long lda, long a_zs, const float* B,
