@@ -525,10 +525,15 @@ class _F16Audit(object):
         self.active, self.records = True, []
 
     def measure(self, key, role, t, rows, cols, ld, bound, outer=0):
+        """outer: 0 = the outer slices are the rows of t as stored, 1 = its columns, or a function that returns the maxima |.| of the
+        outer slices (an operand whose slices are neither, such as the per-cin slices of W^T in a conv's dX)."""
         out = torch.zeros(3, dtype=torch.float32, device=t.device)
         check(load().ams_range_share(_p(t), rows, cols, ld, _p(bound), _p(out), _s()), 'ams_range_share')
         # outer slices entirely below the threshold (index glue of an audit that runs once in ~1000 steps, not a product path)
-        v = torch.as_strided(t, (rows, cols), (ld, 1), t.storage_offset()).abs().amax(dim=1 - outer)
+        if callable(outer):
+            v = outer()
+        else:
+            v = torch.as_strided(t, (rows, cols), (ld, 1), t.storage_offset()).abs().amax(dim=1 - outer)
         slices = torch.stack([((v > 0) & (v < bound * 2.0 ** -17)).sum(), (v > 0).sum()]).to(torch.float32)
         self.records.append((key, role, out, bound, slices))
 
@@ -591,9 +596,11 @@ class lds_pad(object):
 
 # ------------------------------------------------------------------ GEMM
 def gemm(A, B, transA=False, transB=False, bias=None, out=None, accumulate=False, M=None, N=None, K=None,
-         lda=None, ldb=None, ldc=None, mask=(0, 0), label='', amax=None):
+         lda=None, ldb=None, ldc=None, mask=(0, 0), label='', amax=None, key=None):
     """out[M,N] (+)= op(A) op(B) (+ bias).  A/B may be 2-D tensors (dims inferred) or raw views with explicit
-    M,N,K and leading dimensions (for column slices of wider buffers).  amax = (bound of A, bound of B): fp16x3 arithmetic."""
+    M,N,K and leading dimensions (for column slices of wider buffers).  amax = (bound of A, bound of B): fp16x3 arithmetic.
+    key: the product class the range audit keys this launch under, when it is not this launch's own shape (a zero-padded copy of
+    an unaligned product: blstm_input_projection)."""
     lib = load()
     if M is None:
         _chk(A, B, bias)
@@ -621,7 +628,7 @@ def gemm(A, B, transA=False, transB=False, bias=None, out=None, accumulate=False
     nb = lib.ams_gemm_workspace_bytes(M, N, K, 1, pad)
     ws = _ws(nb, A) if nb else None
     ev = PROFILE.begin() if PROFILE.enabled else None
-    pa, pb, gt = _bounds(amax, ('gemm', label, M, N, K, bool(transA), bool(transB)),
+    pa, pb, gt = _bounds(amax, key if key is not None else ('gemm', label, M, N, K, bool(transA), bool(transB)),
                          ((A, K if transA else M, M if transA else K, lda, int(bool(transA))), (B, N if transB else K, K if transB else N, ldb, int(not transB))))
     skp, skn = _sk(A)
     check(lib.ams_gemm_f32(int(transA), int(transB), M, N, K, _p(A), lda, _p(B), ldb, _p(out), ldc, _p(bias), int(accumulate),
@@ -729,8 +736,11 @@ def forward_product(x2, W2, bias, out, amax, label, owner, ldc=None):
     passes for frozen weights); otherwise ams_gemm_f32."""
     M, K = x2.shape
     N = W2.shape[1]
+    if x2.stride(1) != 1 or W2.stride(1) != 1:
+        # (a transposed view: both forms read dense rows at a row pitch; a column stride would be dropped, not honoured)
+        raise AmsError('forward_product: operands with dense rows expected (strides %r, %r)' % (tuple(x2.stride()), tuple(W2.stride())))
     ldc = (out.stride(0) if out.dim() == 2 else N) if ldc is None else ldc
-    if not (forward_product_presplit(M, N, K, out, bias, amax, label, ldc) and x2.stride(1) == 1 and W2.stride(1) == 1):
+    if not forward_product_presplit(M, N, K, out, bias, amax, label, ldc):
         return gemm(x2, W2, bias=bias, out=out, M=M, N=N, K=K, lda=x2.stride(0), ldb=W2.stride(0), ldc=ldc, label=label, amax=amax)
     a_img = ps_pack_rows(x2, amax[0])
     b_img = _ps_weight_image(W2, amax[1], owner)
@@ -992,15 +1002,7 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
     out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
     # ring recurrence: plane 0 = c_t (what every backward reads as `cst`), plane 1 = tanh(c_t) for the backward ring
     cst = torch.empty(((2, B, T, 2, H) if nring else (B, T, 2, H)), dtype=torch.float32, device=x.device)
-    Dp = (D + 3) // 4 * 4
-    if Dp != D and x.is_cuda and not forward_product_presplit(B * T, 8 * H, D, G, bias, amax, 'blstm_input_gemm', 8 * H):
-        # rows of D floats are not 16-byte addressable: project zero-padded copies (x: +3 zero columns, kernels: +3 zero rows)
-        Wp = torch.zeros((Dp, 8 * H), dtype=Wcat.dtype, device=Wcat.device)
-        Wp[:D].copy_(Wcat)
-        gemm(_padded_rows(x2, Dp), Wp, bias=bias, out=G, M=B * T, N=8 * H, K=Dp, lda=Dp, ldb=8 * H, ldc=8 * H, label='blstm_input_gemm',
-             amax=amax)
-    else:
-        forward_product(x2, Wcat, bias, G.view(B * T, 8 * H), amax, 'blstm_input_gemm', Kf)
+    blstm_input_projection(x2, Wcat, bias, G.view(B * T, 8 * H), amax, Kf)
     if nring:
         sync, pre0 = _ring_sync(nring, x)
         check(lib.ams_blstm_ring_fwd(_p(G), _p(out), _p(cst[0]), _p(cst[1]), _p(Kf[D:]), _p(Kb[D:]), ldu,
@@ -1013,9 +1015,29 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
     return out, G, cst
 
 
+def blstm_input_projection(x2, Wcat, bias, G2, amax, owner):
+    """G2 [M, 8H] = x2 [M, D] . Wcat [D, 8H] + bias: the hoisted input projection of both directions of a BLSTM layer, in whichever
+    form applies -- from pre-split images (forward_product_presplit), the product itself on aligned rows, or, for an input width that is
+    not a multiple of 4, a zero-padded copy.  All three are ONE product class for the range audit, keyed by the unpadded shape (K = D):
+    an audit (which runs the padded form: no pre-split form while it is active) and every later pass agree on what it denied."""
+    M, D = x2.shape
+    N = Wcat.shape[1]
+    label = 'blstm_input_gemm'
+    Dp = (D + 3) // 4 * 4
+    if Dp != D and not forward_product_presplit(M, N, D, G2, bias, amax, label, N):
+        # rows of D floats are not 16-byte addressable: project zero-padded copies (x: +3 zero columns, kernels: +3 zero rows)
+        Wp = torch.zeros((Dp, N), dtype=Wcat.dtype, device=Wcat.device)
+        Wp[:D].copy_(Wcat)
+        return gemm(_padded_rows(x2, Dp), Wp, bias=bias, out=G2, M=M, N=N, K=Dp, lda=Dp, ldb=N, ldc=N, label=label, amax=amax,
+                    key=('gemm', label, M, N, D, False, False))
+    return forward_product(x2, Wcat, bias, G2, amax, label, owner)
+
+
 def dense_fwd(x, W, b, amax=None):
     """u = x.W + b over the last axis (utils/ops.py:486-503)."""
     x2 = x.reshape(-1, x.shape[-1])
+    if x2.stride(1) != 1:
+        x2 = x2.contiguous()            # (a transposed view: the product reads dense rows)
     out = torch.empty((x2.shape[0], W.shape[1]), dtype=torch.float32, device=x.device)
     return forward_product(x2, W, b, out, amax, '', W).view(x.shape[:-1] + (W.shape[1],))
 
@@ -1883,9 +1905,13 @@ def dilated_conv2d_fwd(x4, w, b, rate, amax=None, want_amax=True):
     folded by the launch).  amax = (bound of x4, bound of w): fp16x3 products."""
     _chk(x4, w, b)
     g = _conv_args(x4, w, rate)
+    B, T, F_, cin, cout, kh, kw = g[:7]
     y = torch.empty(g[:3] + (g[4],), dtype=torch.float32, device=x4.device)
     ay = torch.empty(1, dtype=torch.float32, device=x4.device) if want_amax else None
-    pa, pb, _ = _bounds(amax)
+    if cin == 1 or cout == 4:
+        amax = None                     # direct f32 kernels (include/ams.h): no product, nothing to bound or audit
+    # A = the pixels of x4 (an output pixel reads a patch of them), B = w as [kh kw cin, cout], outer slices its filter columns
+    pa, pb, _ = _bounds(amax, ('dilated_fwd',) + g, ((x4, B * T * F_, cin, cin, 0), (w, kh * kw * cin, cout, cout, 1)))
     check(load().ams_dilated_conv2d_fwd(_p(x4), _p(w), _p(b), _p(y), *g, pa, pb, _p(ay), _vp(0), 0, _s()), 'ams_dilated_conv2d_fwd')
     return y, ay
 
@@ -1900,7 +1926,9 @@ def dilated_conv2d_bwd_data(dy4, w, y_below, rate, amax=None, want_amax=True):
     dx = torch.empty((B, T, F_, cin), dtype=torch.float32, device=dy4.device)
     adx = torch.empty(1, dtype=torch.float32, device=dy4.device) if want_amax else None
     ws, nb = _conv_ws(g, dy4)
-    pa, pb, _ = _bounds(amax)
+    # A = the pixels of dy4; B = W^T per tap, whose outer slices (what one dx channel is computed from) are w[:, :, ci, :]
+    pa, pb, _ = _bounds(amax, ('dilated_bwd_data',) + g,
+                        ((dy4, B * T * F_, cout, cout, 0), (w, kh * kw * cin, cout, cout, lambda: w.abs().amax(dim=(0, 1, 3)))))
     check(load().ams_dilated_conv2d_bwd_data(_p(dy4), _p(w), _p(y_below), _p(dx), *g, pa, pb, _p(adx), _p(ws), nb, _s()),
           'ams_dilated_conv2d_bwd_data')
     return dx, adx
@@ -1914,7 +1942,11 @@ def dilated_conv2d_bwd_filter(x4, dy4, w, rate, amax=None):
     dw = torch.empty(tuple(w.shape), dtype=torch.float32, device=x4.device)
     db = torch.empty(w.shape[3], dtype=torch.float32, device=x4.device)
     ws, nb = _conv_ws(g, x4)
-    pa, pb, _ = _bounds(amax)
+    B, T, F_, cin, cout = g[:5]
+    if cin < 4 or cout == 4:
+        amax = None                     # not a product of the bounded kind (include/ams.h: cin >= 4, cout > 4)
+    # dw = x^T . dy over the pixels: the outer slices of both operands are channels (columns as stored)
+    pa, pb, _ = _bounds(amax, ('dilated_bwd_filter',) + g, ((x4, B * T * F_, cin, cin, 1), (dy4, B * T * F_, cout, cout, 1)))
     check(load().ams_dilated_conv2d_bwd_filter(_p(x4), _p(dy4), _p(dw), _p(db), *g, pa, pb, _p(ws), nb, _s()),
           'ams_dilated_conv2d_bwd_filter')
     return dw, db

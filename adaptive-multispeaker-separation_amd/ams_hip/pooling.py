@@ -26,7 +26,11 @@ def front_maxpool_fwd(x, f, P, hop):
     # 2 TFLOP of brute-force stride-1 conv: worth two small passes for the operand bounds that let it run as fp16x3
     bounds = (ops.absmax(x), ops.absmax(f)) if ops.F16X3 else None
     ev = ops.PROFILE.begin() if ops.PROFILE.enabled else None
-    pa, pb, gt = ops._bounds(bounds)
+    # audit slices: A = the signals in hop-long segments (a pooled frame reads a few of them; silence next to speech in one signal is
+    # what leaves the range), B = the filters' columns
+    seg = hop if L % hop == 0 else L
+    pa, pb, gt = ops._bounds(bounds, ('front_maxpool', Bt, L, W, N, P, hop),
+                             ((x, Bt, L, L, lambda: x.view(-1, seg).abs().amax(dim=1)), (f, W, N, N, 1)))
     check(lib.ams_front_maxpool_fwd(_p(x), _p(f), _p(y), _p(am), Bt, L, W, N, P, hop, pa, pb, _p(ws), nb, _s()), 'ams_front_maxpool_fwd')
     if ev is not None:
         ops.PROFILE.end(ev, 2.0 * Bt * L * N * W, 4.0 * (Bt * L + W * N + Bt * T * N), gt)
