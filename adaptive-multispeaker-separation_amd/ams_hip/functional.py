@@ -929,6 +929,74 @@ def l41_loss(emb, y, speaker_vectors, I, normalize, neg_idx=None, ns_rate=0.1, f
     return L41LossNS.apply(_c(emb).reshape(B, -1, E), _c(y).reshape(B, -1, S), vs, negs, float(ns_rate), bool(from_u))
 
 
+class DanetRecon(Function):
+    """models/SC_V2.py:66-92: attractors from the ideal masks, sigmoid assignments, squared reconstruction error.  Gradient w.r.t. the
+    embeddings only (csrc/danet.hip)."""
+
+    @staticmethod
+    def forward(ctx, u, y, x_input, x_non_mix, x_sil, thr):
+        cost, attr, g, dattr = ops.danet_recon_fwd(u, y, x_input, x_non_mix, x_sil, thr, want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(y, x_sil, attr, g, dattr)
+        ctx.thr = thr
+        return cost
+
+    @staticmethod
+    def backward(ctx, gc):
+        y, x_sil, attr, g, dattr = ctx.saved_tensors
+        return ops.danet_recon_bwd(y, g, attr, dattr, _c(gc), x_sil, ctx.thr), None, None, None, None, None
+
+
+def _danet_args(u, y, x_input, x_non_mix, x_for_silence, thr, E):
+    B = u.shape[0]
+    S = y.shape[-1]
+    u3 = _c(u).reshape(B, -1, E)
+    if x_for_silence is not None and thr is None:
+        raise ValueError('danet_recon_loss: x_for_silence needs thr')
+    xs = _c(x_for_silence).reshape(B, -1) if x_for_silence is not None else None
+    return u3, _c(y).reshape(B, -1, S), _c(x_input).reshape(B, -1), x_non_mix, xs, (float(thr) if xs is not None else None)
+
+
+def danet_recon_loss(u, y, x_input, x_non_mix, x_for_silence=None, thr=None):
+    """Deep-attractor reconstruction cost of L41ModelV2 (models/SC_V2.py:66-92).  u [B,T,F,E] the embeddings as the network emits them, y [B,T,F,S] masks with m = (y + 1) / 2 (any float weights), x_input [B,T,F], x_non_mix
+    [B,T,F,S] (the permuted view of the [B*S,T,F] rows is read in place).  x_for_silence [B,T,F] with thr: m also carries the mask
+    log10(max |x| / |x|) < thr.  Returns the scalar cost [1]; gradient w.r.t. u only."""
+    return DanetRecon.apply(*_danet_args(u, y, x_input, x_non_mix, x_for_silence, thr, u.shape[-1]))
+
+
+class DanetSceLoss(Function):
+    """L41ModelV2.cost (models/SC_V2.py:44-127) on gathered speaker vectors: the source-contrastive cost of L41Loss(from_u) on y_ab plus
+    the reconstruction cost of DanetRecon on y, as ONE node, so that the backward ADDS the reconstruction gradient into the tensor the
+    source-contrastive backward wrote (one read-modify-write, no second full-size gradient, no torch add; the bound of the sum comes out
+    of the same pass).  Returns (total, source-contrastive, reconstruction); only `total` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, u, y_ab, vspk, y, x_input, x_non_mix, x_sil, thr):
+        sc = ops.l41_loss_fwd(u, y_ab, vspk, True)
+        rc, attr, g, dattr = ops.danet_recon_fwd(u, y, x_input, x_non_mix, x_sil, thr, want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(u, y_ab, vspk, y, x_sil, attr, g, dattr)
+        ctx.thr = thr
+        ctx.mark_non_differentiable(sc, rc)
+        return sc + rc, sc, rc
+
+    @staticmethod
+    def backward(ctx, gt, _gsc, _grc):
+        u, y_ab, vspk, y, x_sil, attr, g, dattr = ctx.saved_tensors
+        gt = _c(gt)
+        demb, dvs = ops.l41_loss_bwd(u, y_ab, vspk, gt, True)
+        demb = ops.danet_recon_bwd(y, g, attr, dattr, gt, x_sil, ctx.thr, into=demb)
+        return demb, None, dvs, None, None, None, None, None
+
+
+def danet_sce_loss(u, y_ab, y, speaker_vectors, I, x_input, x_non_mix, x_for_silence=None, thr=None):
+    """cost of L41ModelV2 = F.l41_loss(u, y_ab, speaker_vectors, I, True, from_u=True) + F.danet_recon_loss(u, y, ...) with the two
+    backward passes chained on one gradient tensor (DanetSceLoss).  -> (total, source_contrastive, reconstruction), [1] each."""
+    B, E = u.shape[0], speaker_vectors.shape[1]
+    S = y.shape[-1]
+    vs = L41Speakers.apply(_c(speaker_vectors), I, True)                                   # [B,S,E], l2-normalised rows
+    u3, y3, xi, xnm, xs, thr = _danet_args(u, y, x_input, x_non_mix, x_for_silence, thr, E)
+    return DanetSceLoss.apply(u3, _c(y_ab).reshape(B, -1, S), vs, y3, xi, xnm, xs, thr)
+
+
 class EnhanceOutput(Function):
     """Separator.enhance output stage (network.py:640-660): act over the speaker axis, times X; two layouts out."""
 

@@ -1814,6 +1814,63 @@ def l41_loss_ns_bwd(emb, y, vspk, negs, upstream, ns_rate, from_u=False):
     return demb, dvs, dnegs
 
 
+# ------------------------------------------------------------------ DANet reconstruction loss (models/SC_V2.py:44-92)
+def _xnm_layout(x_non_mix, B, TF, S):
+    """x_non_mix as the kernels read it: (tensor, rows flag).  [B,S,TF] rows (what the front / the STFT writes, also behind the
+    permuted [B,T,F,S] view the separator holds) are read in place; anything else as a contiguous [B,TF,S]."""
+    if x_non_mix.dim() == 3 and tuple(x_non_mix.shape) == (B, S, TF) and x_non_mix.is_contiguous():
+        return x_non_mix, 1
+    if x_non_mix.dim() == 4 and x_non_mix.shape[0] == B and x_non_mix.shape[3] == S and not x_non_mix.is_contiguous():
+        rows = x_non_mix.permute(0, 3, 1, 2)
+        if rows.is_contiguous():
+            return rows, 1
+    return x_non_mix.reshape(B, TF, S).contiguous(), 0
+
+
+def danet_recon_fwd(v, y, x_input, x_non_mix, x_sil=None, thr=None, want_grad=True):
+    """v [B,TF,E], y [B,TF,S], x_input [B,TF], x_non_mix [B,S,TF] rows or [B,T,F,S] / [B,TF,S]; x_sil [B,TF] with thr: the silence mask.
+    -> cost [1], and (attr [B,S,E], g [B,TF,S], dattr [B,S,E]) for danet_recon_bwd (g, dattr None without want_grad)."""
+    B, TF, E = v.shape
+    S = y.shape[2]
+    xnm, rows = _xnm_layout(x_non_mix, B, TF, S)
+    _chk(v, y, x_input, xnm, x_sil)
+    if x_input.numel() != B * TF or xnm.numel() != B * TF * S or (x_sil is not None and x_sil.numel() != B * TF):
+        raise AmsError('danet_recon: x_input / x_non_mix / x_sil do not match v %s, y %s' % (tuple(v.shape), tuple(y.shape)))
+    if x_sil is not None and thr is None:
+        raise AmsError('danet_recon: the silence mask needs its threshold')
+    lib = load()
+    nb = lib.ams_danet_workspace_bytes(B, TF, E, S)
+    ws = _ws(nb, v)
+    cost = torch.empty(1, dtype=torch.float32, device=v.device)
+    attr = torch.empty((B, S, E), dtype=torch.float32, device=v.device)
+    g = torch.empty((B, TF, S), dtype=torch.float32, device=v.device) if want_grad else None
+    dattr = torch.empty_like(attr) if want_grad else None
+    check(lib.ams_danet_recon_fwd(_p(v), _p(y), _p(x_sil), float(thr or 0.0), _p(x_input), _p(xnm), rows, _p(cost), _p(attr), _p(g), _p(dattr),
+                                  B, TF, E, S, _p(ws), nb, _s()), 'ams_danet_recon_fwd')
+    return cost, attr, g, dattr
+
+
+def danet_recon_bwd(y, g, attr, dattr, upstream, x_sil=None, thr=None, into=None):
+    """d cost / d v * upstream [B,TF,E].  into: a gradient of that shape (the source-contrastive one) the result is ADDED to in place --
+    returned, with the bound of the sum attached (the tag tag_amax left on `into` dies with the write)."""
+    _chk(y, g, attr, dattr, upstream, x_sil, into)
+    lib = load()
+    B, TF, S = g.shape
+    E = attr.shape[2]
+    nb = lib.ams_danet_workspace_bytes(B, TF, E, S)
+    ws = _ws(nb, g)
+    dv = into if into is not None else torch.empty((B, TF, E), dtype=torch.float32, device=g.device)
+    if tuple(dv.shape) != (B, TF, E):
+        raise AmsError('danet_recon_bwd: `into` is %s, the gradient [%d, %d, %d]' % (tuple(dv.shape), B, TF, E))
+    am = torch.empty(1, dtype=torch.float32, device=g.device) if F16X3 else None
+    check(lib.ams_danet_recon_bwd(_p(y), _p(x_sil), float(thr or 0.0), _p(g), _p(attr), _p(dattr), _p(upstream), _p(dv), int(into is not None),
+                                  _p(am), B, TF, E, S, _p(ws), nb, _s()), 'ams_danet_recon_bwd')
+    if hasattr(dv, '_ams_amax'):
+        del dv._ams_amax                                     # (the kernel wrote behind torch's version counter)
+    tag_amax(dv, am)
+    return dv
+
+
 # ------------------------------------------------------------------ k-means
 def kmeans_normalize(x):
     _chk(x)

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 7
+#define AMS_ABI_VERSION 8
 
 typedef int32_t ams_status;
 #define AMS_OK 0
@@ -476,6 +476,26 @@ ams_status ams_l41_loss_ns_fwd(const float* emb, const float* y, const float* vs
 ams_status ams_l41_loss_ns_bwd(const float* emb, const float* y, const float* vspk, const float* negs, const float* upstream, float* demb,
                                float* dvspk, float* dnegs, float* amax_out, int B, long TF, int E, int S, int NSEL, int K, float ns_rate,
                                int emb_is_u, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- deep-attractor reconstruction loss of the DANet-SCE separator (ABI 8)   models/SC_V2.py:44-92 ----
+ *   m = (y + 1) / 2 (* the silence mask [log10(max |x_sil[b,:]| / |x_sil[b,p]|) < sil_thr] when x_sil != NULL): a float weight
+ *   attr[b,s,:] = sum_p v[b,p,:] m[b,p,s] / (1e-12 + sum_p m[b,p,s]);   a = sigmoid(<attr[b,s,:], v[b,p,:]>)
+ *   cost[0] = mean_b mean_s mean_p (x_non_mix[b,p,s] - x_input[b,p] a[b,p,s])^2
+ * v [B,TF,E] the embeddings as the network emits them (NOT normalised), y [B,TF,S], x_sil / x_input [B,TF], x_non_mix [B,S,TF]
+ * (xnm_rows != 0: the rows the front / the STFT writes) or [B,TF,S] (xnm_rows = 0).  Same (E, S) domain as ams_l41_loss_fwd.
+ * Forward: two reads of v.  g [B,TF,S] and dattr [B,S,E] (both or neither; NULL = cost only) receive what the backward needs:
+ * g = d cost / d logit and dattr = (sum_p g v) / (1e-12 + sum_p m).  Backward: dv = upstream[0] * sum_s (g attr + m dattr) -- no read
+ * of v; accumulate != 0 ADDS it to what dv holds (the gradient ams_l41_loss_bwd wrote: one read-modify-write, no temporary);
+ * amax_out (optional): ONE float that receives max |dv| as the launch leaves it.  Pass the forward's y, x_sil, sil_thr.
+ * All sums over p are two-stage (256-point blocks in a fixed order, then the blocks in a fixed order), no atomics: same inputs, same
+ * bits.  Nothing synchronises: both calls capture into a hipGraph. */
+size_t ams_danet_workspace_bytes(int B, long TF, int E, int S);
+ams_status ams_danet_recon_fwd(const float* v, const float* y, const float* x_sil, float sil_thr, const float* x_input, const float* x_non_mix,
+                               int xnm_rows, float* cost, float* attr, float* g, float* dattr, int B, long TF, int E, int S, void* ws,
+                               size_t ws_bytes, void* stream);
+ams_status ams_danet_recon_bwd(const float* y, const float* x_sil, float sil_thr, const float* g, const float* attr, const float* dattr,
+                               const float* upstream, float* dv, int accumulate, float* amax_out, int B, long TF, int E, int S, void* ws,
+                               size_t ws_bytes, void* stream);
 
 /* ---- K16-K19 batched k-means   models/Kmeans_2.py:40-188 ----
  * xn [b,L,E] normalised input (ams_kmeans_normalize); rows r = b_idx*tries + try; centroids [b*tries, C, E];

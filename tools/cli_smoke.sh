@@ -25,6 +25,7 @@ FT="--learning_rate 0.0001 --optimizer RMSProp --nb_tries 1 --nb_steps 5 --beta_
 for g in "" "--hip_graph"; do
     run front_DPCL $COMMON --model_folder $P --learning_rate 0.001 $g
     run front_L41 $COMMON --model_folder $P --learning_rate 0.001 $g
+    run front_L41V2 $COMMON --model_folder $P --learning_rate 0.001 $g
 done
 D=$(last front_DPCL); Q=$(last front_L41)
 for g in "" "--hip_graph"; do
@@ -42,6 +43,7 @@ STFT="--window_size 512 --hop_size 256"
 for g in "" "--hip_graph"; do
     run STFT_DPCL $COMMON $STFT --learning_rate 0.001 $g
     run STFT_L41 $COMMON $STFT --learning_rate 0.001 $g
+    run STFT_L41V2 $COMMON $STFT --learning_rate 0.001 $g
 done
 SD=$(last STFT_DPCL); SL=$(last STFT_L41)
 for g in "" "--hip_graph"; do
