@@ -1668,7 +1668,8 @@ def pair_stats_bwd(target, est, gstats):
 
 
 def pair_combine_fwd(stats, D2, perms, S, mode, cl, cs):
-    """Costs from the pair table in one launch (csrc/synth.hip pair_combine_*): returns (out [2], pbest, jbest)."""
+    """Costs from the pair table in one launch (csrc/synth.hip pair_combine_*): returns (out [2], pbest, jbest).  The entry point picks
+    the path by S: above four speakers (modes 1, 2) the permutation search is a launch of its own in front (pair_search_kernel)."""
     _chk(stats)
     B = stats.shape[0]
     dev = stats.device

@@ -520,6 +520,221 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// HARD_ACC for five and six clusters.  kmeans_pass_kernel keeps all C (E + 1) running sums of a lane live at once: 205 / 246 values at
+// E = 40 under the 168-register bound -- 528-740 bytes of scratch per lane.  Here the chunk is swept once per GROUP of two clusters
+// with that group's sums (82 at E = 40, what C = 2 carries) in registers: the first sweep computes the point's label exactly as
+// kmeans_pass_kernel does and keeps it (32 labels per lane, four bits each, two 64-bit registers), the later ones read the label
+// back and the point again (from L2: the chunk was just read).  The sums of different clusters never meet, so every sum sees the
+// same terms in the same order as in the one-sweep form: same bits (tests/test_gpu_many_speakers_kernels.py against oracle/kmeans.py).
+// Work order, staging, distance chains, lane trees and the in-launch finish are kmeans_pass_kernel's.
+// Measured, one pass at b = 64, tries = 10, L = 20480, E = 40: C = 5 / 6 take 2.40 / 3.22 ms in kmeans_pass_kernel,
+// 1.01 / 2.24 ms in groups of three (220-328 bytes of scratch) and 0.64 / 0.74 ms in groups of two (60-108 bytes).
+#ifndef AMS_KM_GROUPED
+#define AMS_KM_GROUPED 1        // 0: C = 5, 6 accumulate in kmeans_pass_kernel (A/B build: make variant FLAGS=-DAMS_KM_GROUPED=0)
+#endif
+#ifndef AMS_KM_GROUP_SIZE
+#define AMS_KM_GROUP_SIZE 2     // clusters per sweep (2 or 3)
+#endif
+template <int E_, int C_, bool HAS_W>
+__global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_kernel(KmArgs a) {
+    static_assert(E_ % 4 == 0 && C_ > 4 && C_ <= 6, "labels are kept in four bits");
+    constexpr int GS = AMS_KM_GROUP_SIZE, NG = (C_ + GS - 1) / GS, NV = C_ * (E_ + 1);
+    static_assert(NG <= 3, "at most three sweeps");
+    constexpr int CHUNK = CHUNK_HARD, PPL = CHUNK / LANES;
+    static_assert(PPL == 32, "32 labels per lane in two 64-bit registers");
+    constexpr int LD = E_ + 4, V4 = E_ / 4;
+    __shared__ __attribute__((aligned(16))) float buf[256 * LD];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int r, g;
+    {
+        const int M = a.G * a.tries, xcd = blockIdx.x & 7, n = blockIdx.x >> 3;
+        const int ub = (n / M) * 8 + xcd, m = n - (n / M) * M;
+        if (ub >= a.b) return;
+        g = m / a.tries;
+        r = ub * a.tries + (m - g * a.tries);
+    }
+    const int bi = r / a.tries;
+    const float* xb = a.xn + (long)bi * a.L * E_;
+    const float* wb = HAS_W ? a.w + (long)(a.w_mod_b ? (r % a.b) : bi) * a.L : nullptr;
+    unsigned long long lab_lo = 0ull, lab_hi = 0ull;               // labels of this lane's points j = 0..15 / 16..31
+    float* wbuf = buf + wave * 64 * LD;
+
+    auto sweep = [&](auto GT) {
+        constexpr int G = decltype(GT)::value, C0 = G * GS, CN = (C_ - C0 < GS) ? C_ - C0 : GS;
+        // first sweep: the row's centroids as scalar operands of the distance chains (see kmeans_pass_kernel)
+        float cs[G == 0 ? C_ * E_ : 1];
+        if (G == 0) {
+            const float* cg = a.cent + (long)r * C_ * E_;
+#pragma unroll
+            for (int i = 0; i < C_ * E_; ++i)
+                cs[i % (G == 0 ? C_ * E_ : 1)] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cg[i])));
+        }
+        float acc[CN * (E_ + 1)];
+#pragma unroll
+        for (int i = 0; i < CN * (E_ + 1); ++i) acc[i] = 0.f;
+        float4 pre[V4];
+        auto fetch = [&](int j) {
+            const long q0 = (long)g * CHUNK + (long)j * LANES + wave * 64;
+            const int np = (int)max((long)0, min((long)64, a.L - q0));
+            const float4* src = reinterpret_cast<const float4*>(xb + q0 * E_);
+#pragma unroll
+            for (int k = 0; k < V4; ++k) {
+                const int i = lane + 64 * k;
+                pre[k] = (i < np * V4) ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        };
+        fetch(0);
+        for (int j = 0; j < PPL; ++j) {
+            const long p0 = (long)g * CHUNK + (long)j * LANES;
+            const int npts = (int)max((long)0, min((long)LANES, a.L - p0));
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // this wave's reads of the previous slab are complete
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < V4; ++k) {
+                const int i = lane + 64 * k;
+                const int row = i / V4, c4 = i - row * V4;
+                *reinterpret_cast<float4*>(&wbuf[row * LD + c4 * 4]) = pre[k];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            if (j + 1 < PPL) fetch(j + 1);
+            if (tid < npts) {
+                const float* xrow = &buf[tid * LD];
+                asm volatile("" ::: "memory");
+                const float wv = HAS_W ? wb[p0 + tid] : 1.0f;
+                const f2 wv2 = {wv, wv};
+                int lab = 0;
+                if (G == 0) {
+                    // d2[c] = sum over e, left to right, of (x_e - c_e)^2 w: the packed chains of kmeans_pass_kernel, two clusters a register
+                    constexpr int CP = (C_ + 1) / 2;
+                    f2 dp[CP];
+#pragma unroll
+                    for (int cp = 0; cp < CP; ++cp) dp[cp] = (f2){0.f, 0.f};
+                    float4 vd[2];
+                    vd[0] = *reinterpret_cast<const float4*>(xrow);
+#pragma unroll
+                    for (int q4 = 0; q4 < V4; ++q4) {
+                        asm volatile("" ::: "memory");
+#pragma unroll
+                        for (int cp = 0; cp < CP; ++cp) asm volatile("" : "+v"(dp[cp]));
+                        if (q4 + 1 < V4) vd[(q4 + 1) % 2] = *reinterpret_cast<const float4*>(xrow + (q4 + 1) * 4);
+                        const float4 v = vd[q4 % 2];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const float xe = k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
+                            const f2 xx = {xe, xe};
+#pragma unroll
+                            for (int cp = 0; cp < CP; ++cp) {
+                                const int c0 = 2 * cp, c1 = (2 * cp + 1 < C_) ? 2 * cp + 1 : 2 * cp;
+                                const f2 cc = {cs[(c0 * E_ + 4 * q4 + k) % (G == 0 ? C_ * E_ : 1)], cs[(c1 * E_ + 4 * q4 + k) % (G == 0 ? C_ * E_ : 1)]};
+                                const f2 df = xx - cc;
+                                const f2 sq = df * df;                       // rounded on its own (contraction is off in this unit)
+                                dp[cp] = dp[cp] + (HAS_W ? sq * wv2 : sq);
+                            }
+                        }
+                    }
+                    float best = sqrtf(dp[0].x);
+#pragma unroll
+                    for (int c = 1; c < C_; ++c) {
+                        const float dc = sqrtf((c & 1) ? dp[c / 2].y : dp[c / 2].x);
+                        if (dc < best) { best = dc; lab = c; }
+                    }
+                    const unsigned long long bits = (unsigned long long)lab << (4 * (j & 15));
+                    if (j < 16) lab_lo |= bits; else lab_hi |= bits;
+                } else {
+                    lab = (int)(((j < 16 ? lab_lo : lab_hi) >> (4 * (j & 15))) & 15ull);
+                }
+                f2 mm[CN];
+#pragma unroll
+                for (int c = 0; c < CN; ++c) {
+                    const float m = (lab == C0 + c) ? 1.0f : 0.0f;
+                    mm[c] = (f2){m, m};
+                    acc[CN * E_ + c] = __fadd_rn(acc[CN * E_ + c], m);
+                }
+                float4 vq[2];
+                asm volatile("" ::: "memory");
+                vq[0] = *reinterpret_cast<const float4*>(xrow);
+#pragma unroll
+                for (int q4 = 0; q4 < V4; ++q4) {
+                    asm volatile("" ::: "memory");
+                    if (q4 + 1 < V4) vq[(q4 + 1) % 2] = *reinterpret_cast<const float4*>(xrow + (q4 + 1) * 4);
+                    const float4 v = vq[q4 % 2];
+                    f2 t0 = {v.x, v.y}, t1 = {v.z, v.w};
+                    if (HAS_W) { t0 = t0 * wv2; t1 = t1 * wv2; }
+#pragma unroll
+                    for (int c = 0; c < CN; ++c) {
+                        f2 a0 = {acc[c * E_ + 4 * q4], acc[c * E_ + 4 * q4 + 1]};
+                        f2 a1 = {acc[c * E_ + 4 * q4 + 2], acc[c * E_ + 4 * q4 + 3]};
+                        // m is 0 or 1, so t * m is exact and the fused form rounds exactly like multiply-then-add
+                        a0 = __builtin_elementwise_fma(t0, mm[c], a0);
+                        a1 = __builtin_elementwise_fma(t1, mm[c], a1);
+                        acc[c * E_ + 4 * q4] = a0.x; acc[c * E_ + 4 * q4 + 1] = a0.y;
+                        acc[c * E_ + 4 * q4 + 2] = a1.x; acc[c * E_ + 4 * q4 + 3] = a1.y;
+                    }
+                }
+            }
+        }
+        // every wavefront a partial of its own: the halving tree of kmeans_pass_kernel; the group's values go to their places among the NV
+#pragma unroll
+        for (int i = 0; i < CN * (E_ + 1); ++i) {
+            float v = acc[i];
+            v = __fadd_rn(v, lane_above<32>(v));
+            v = __fadd_rn(v, lane_above<16>(v));
+            v = __fadd_rn(v, lane_above<8>(v));
+            v = __fadd_rn(v, lane_above<4>(v));
+            v = __fadd_rn(v, lane_above<2>(v));
+            v = __fadd_rn(v, lane_above<1>(v));
+            if (lane == 0) {
+                const int k = i < CN * E_ ? C0 * E_ + i : C_ * E_ + C0 + (i - CN * E_);
+                float* const dst = a.part + (((long)r * a.G + g) * 4 + wave) * NV + k;
+                if (a.tickets) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through: read by the finisher
+                else *dst = v;
+            }
+        }
+    };
+    sweep(std::integral_constant<int, 0>{});
+    sweep(std::integral_constant<int, 1>{});
+    if constexpr (NG > 2) sweep(std::integral_constant<int, 2>{});
+    if (a.tickets == nullptr) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's partial is acknowledged before the barrier below
+    __shared__ int last_sh;
+    __syncthreads();                                               // all four wavefronts' partials are out
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int last = atomicAdd(a.tickets + r, 1u) == (unsigned)a.G - 1u;
+        if (last) __hip_atomic_store(a.tickets + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_sh = last;
+    }
+    __syncthreads();
+    if (!last_sh || tid >= C_ * E_) return;
+    // the row's last chunk: its 4 G partial rows added in (chunk, wavefront) order, eight loads in flight (kmeans_pass_kernel)
+    const int NP = a.G * 4;
+    const float* pr = a.part + (long)r * NP * NV;
+    auto chunk_sum = [&](int k) {
+        float s = 0.f;
+        int gg = 0;
+        for (; gg + 8 <= NP; gg += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = __hip_atomic_load(pr + (long)(gg + j) * NV + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s = __fadd_rn(s, v[j]);
+        }
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (gg + j < NP) ? __hip_atomic_load(pr + (long)min(gg + j, NP - 1) * NV + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (gg + j < NP) s = __fadd_rn(s, v[j]);
+        return s;
+    };
+    const int c = tid / E_;
+    const float num = chunk_sum(tid), den = chunk_sum(C_ * E_ + c);
+    a.fin_out[(long)r * C_ * E_ + tid] = ((num) / (den));
+    if (a.fin_den && (tid % E_) == 0) a.fin_den[(long)r * C_ + c] = den;
+}
+
 // Sum the G partial rows of a row in order; ACC passes: centroid = num / den.  FINAL passes: inertia[r] = sum_c tot_c/cnt_c.
 __global__ void kmeans_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, float* __restrict__ den_out, int R,
                                      int G, int C, int E, int final_) {
@@ -1201,6 +1416,10 @@ ams_status launch_pass(const KmArgs& a, int R, int E, int C, hipStream_t st) {
     else if (E == 8 && C == 4) AMS_KM(8, 4);
     else if (E == 20 && C == 2) AMS_KM(20, 2);
     else if (E == 20 && C == 3) AMS_KM(20, 3);
+    else if (E == 40 && C == 5) AMS_KM(40, 5);                     // five and six clusters: the recipes' E = 40 and the reduced-size E = 8
+    else if (E == 40 && C == 6) AMS_KM(40, 6);
+    else if (E == 8 && C == 5) AMS_KM(8, 5);
+    else if (E == 8 && C == 6) AMS_KM(8, 6);
     else return AMS_E_INVALID_ARG;
 #undef AMS_KM
     return ams_check_launch();
@@ -1251,7 +1470,7 @@ ams_status ams_kmeans_init(const float* xn, const int32_t* init_idx, float* cent
 // beta < 0: hard assignment (argmin), else soft assignment softmax(-beta d^2).
 ams_status ams_kmeans_iterate(const float* xn, const float* w, const float* cent_in, float* cent_out, float* den_out, int b, int tries,
                               long L, int E, int C, float beta, int w_mod_b, void* ws, size_t ws_bytes, void* tickets, void* stream) {
-    AMS_REQUIRE(xn && cent_in && cent_out && ws && b > 0 && tries > 0 && L > 0 && C >= 2 && C <= 4);
+    AMS_REQUIRE(xn && cent_in && cent_out && ws && b > 0 && tries > 0 && L > 0 && C >= 2 && C <= 6);
     const int R = b * tries;
     if (ws_bytes < ams_kmeans_workspace_bytes(R, L, E, C)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
@@ -1289,7 +1508,7 @@ ams_status ams_kmeans_iterate(const float* xn, const float* w, const float* cent
         const dim3 grid(k.nG, R);
 #define AMS_KSF(CC) do { if (w) hipLaunchKernelGGL((kmeans_soft_acc_kernel<CC, true>), grid, dim3(256), 0, st, k); \
                          else hipLaunchKernelGGL((kmeans_soft_acc_kernel<CC, false>), grid, dim3(256), 0, st, k); } while (0)
-        if (C == 2) AMS_KSF(2); else if (C == 3) AMS_KSF(3); else AMS_KSF(4);
+        if (C == 2) AMS_KSF(2); else if (C == 3) AMS_KSF(3); else if (C == 4) AMS_KSF(4); else if (C == 5) AMS_KSF(5); else AMS_KSF(6);
 #undef AMS_KSF
         ams_status s2 = ams_check_launch();
         if (s2 != AMS_OK || tickets) return s2;
@@ -1297,7 +1516,18 @@ ams_status ams_kmeans_iterate(const float* xn, const float* w, const float* cent
                            k.nG, C, E, 0);
         return ams_check_launch();
     }
-    ams_status s = beta < 0.f ? launch_pass<HARD_ACC>(a, R, E, C, st) : launch_pass<SOFT_ACC>(a, R, E, C, st);
+    ams_status s;
+    if (AMS_KM_GROUPED && beta < 0.f && C > 4 && (E == 40 || E == 8)) {
+        // five and six clusters: three sweeps of the chunk, two clusters' sums at a time (kmeans_hard_acc_grouped_kernel)
+        dim3 grid((unsigned)(ceil_div(b, 8) * 8 * a.G * tries));
+#define AMS_KMG(EE, CC) do { if (w) hipLaunchKernelGGL((kmeans_hard_acc_grouped_kernel<EE, CC, true>), grid, dim3(256), 0, st, a); \
+                             else hipLaunchKernelGGL((kmeans_hard_acc_grouped_kernel<EE, CC, false>), grid, dim3(256), 0, st, a); } while (0)
+        if (E == 40 && C == 5) AMS_KMG(40, 5); else if (E == 40) AMS_KMG(40, 6); else if (C == 5) AMS_KMG(8, 5); else AMS_KMG(8, 6);
+#undef AMS_KMG
+        s = ams_check_launch();
+    } else {
+        s = beta < 0.f ? launch_pass<HARD_ACC>(a, R, E, C, st) : launch_pass<SOFT_ACC>(a, R, E, C, st);
+    }
     if (s != AMS_OK || tickets) return s;
     hipLaunchKernelGGL(kmeans_reduce_kernel, dim3(ceil_div((long)R * C * E, 256)), dim3(256), 0, st, (const float*)ws, cent_out, den_out, R,
                        beta < 0.f ? 4 * a.G : a.G, C, E, 0);
@@ -1307,7 +1537,7 @@ ams_status ams_kmeans_iterate(const float* xn, const float* w, const float* cent
 // Labels for `cent` (+ per-row inertia).  hard: labels int32 [R,L]; soft: soft [R,L,C].  Either output may be NULL.
 ams_status ams_kmeans_assign(const float* xn, const float* w, const float* cent, int32_t* labels, float* soft, float* inertia, int b,
                              int tries, long L, int E, int C, float beta, int w_mod_b, void* ws, size_t ws_bytes, void* tickets, void* stream) {
-    AMS_REQUIRE(xn && cent && ws && b > 0 && tries > 0 && L > 0 && C >= 2 && C <= 4);
+    AMS_REQUIRE(xn && cent && ws && b > 0 && tries > 0 && L > 0 && C >= 2 && C <= 6);
     const int R = b * tries;
     if (ws_bytes < ams_kmeans_workspace_bytes(R, L, E, C)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;

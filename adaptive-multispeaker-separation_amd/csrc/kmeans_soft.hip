@@ -40,8 +40,10 @@ inline int ks_chunks(int b, long L) {
 typedef const float __attribute__((address_space(4))) ks_cfloat;
 __device__ __forceinline__ ks_cfloat* ks_const(const float* p) { return (ks_cfloat*)p; }
 
-// constants record of one (utterance, iteration): [cent C*E | dnum C*E | dden C, padded to 4 | |cent_c|^2 C, padded to 4]
-template <int E_, int C_> struct KsRec { static constexpr int CE = C_ * E_, N = 2 * CE + 8; };
+// constants record of one (utterance, iteration): [cent C*E | dnum C*E | dden C, padded to PAD | |cent_c|^2 C, padded to PAD]
+// (PAD = 4 up to four clusters -- the layout those have always had -- and 8 for five and six)
+__host__ __device__ constexpr int ks_pad(int C) { return C <= 4 ? 4 : 8; }
+template <int E_, int C_> struct KsRec { static constexpr int CE = C_ * E_, PAD = ks_pad(C_), N = 2 * CE + 2 * PAD; };
 typedef float ks_f2 __attribute__((ext_vector_type(2)));
 typedef const ks_f2 __attribute__((address_space(4))) ks_cf2;
 
@@ -68,7 +70,7 @@ __global__ void ks_init_kernel(KsArgs a) {
     const float* cf = a.cents + ((long)a.n_it * a.b + r) * R::CE;
     for (int i = tid; i < R::N; i += blockDim.x) {
         float v = i < R::CE ? cf[i] : 0.f;
-        if (i >= 2 * R::CE + 4 && i < 2 * R::CE + 4 + C_) { v = 0.f; for (int e = 0; e < E_; ++e) v = fmaf(cf[(i - 2 * R::CE - 4) * E_ + e], cf[(i - 2 * R::CE - 4) * E_ + e], v); }
+        if (i >= 2 * R::CE + R::PAD && i < 2 * R::CE + R::PAD + C_) { v = 0.f; for (int e = 0; e < E_; ++e) v = fmaf(cf[(i - 2 * R::CE - R::PAD) * E_ + e], cf[(i - 2 * R::CE - R::PAD) * E_ + e], v); }
         rec[i] = v;
     }
     for (int i = tid; i < R::CE; i += blockDim.x) a.G[((long)a.n_it * a.b + r) * R::CE + i] = a.dsel ? a.dsel[(long)r * R::CE + i] : 0.f;
@@ -91,7 +93,7 @@ __device__ __forceinline__ void ks_point(const ks_f2 (&x2)[E_ / 2], float xx, ks
         ks_f2 s = {0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < H; ++q) s = __builtin_elementwise_fma(x2[q], (ks_f2)rec2[c * H + q], s);
-        d[c] = wv * (xx - 2.0f * (s[0] + s[1]) + rec[2 * CE + 4 + c]);
+        d[c] = wv * (xx - 2.0f * (s[0] + s[1]) + rec[2 * CE + ks_pad(C_) + c]);
     }
     float sum = 0.f;
 #pragma unroll
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(256) void ks_pass_kernel(KsArgs a, int it) {
             float dsum = 0.f, cc = 0.f;
             for (int e = 0; e < E_; ++e) { dsum += gfin[tid * E_ + e] * ccur[tid * E_ + e]; cc = fmaf(cprev[tid * E_ + e], cprev[tid * E_ + e], cc); }
             nrec[2 * CE + tid] = -dsum / den[tid];
-            nrec[2 * CE + 4 + tid] = cc;
+            nrec[2 * CE + R::PAD + tid] = cc;
         }
     }
     if (tid == 0) a.ticket[r] = 0u;                            // for the next pass (stream order)
@@ -454,7 +456,7 @@ extern "C" {
 size_t ams_kmeans_soft_bwd_workspace_bytes(int b, long L, int E, int C, int n_it) {
     if (b <= 0 || L <= 0 || E <= 0 || C <= 0 || n_it < 0) return 0;
     const size_t nG = (size_t)ks_chunks(b, L), CE = (size_t)C * E;
-    return ks_align((size_t)b * nG * (CE + C) * 4) + ks_align((size_t)b * (n_it + 1) * (2 * CE + 8) * 4) + ks_align((size_t)(n_it + 1) * b * CE * 4) +
+    return ks_align((size_t)b * nG * (CE + C) * 4) + ks_align((size_t)b * (n_it + 1) * (2 * CE + 2 * ks_pad(C)) * 4) + ks_align((size_t)(n_it + 1) * b * CE * 4) +
            ks_align((size_t)b * 4) + 256;
 }
 // byte offset, inside that workspace, of max |dx| (a float): valid after ams_kmeans_soft_bwd -- the operand bound of the products that read dx
@@ -473,7 +475,7 @@ size_t ams_kmeans_soft_bwd_amax_offset(int b, long L, int E, int C, int n_it) {
 ams_status ams_kmeans_soft_bwd(const float* xn, const float* w, const float* w_final, const float* cents, const float* dens, const float* dsel,
                                const float* dout, const float* inv, const float* inv0, const int32_t* seed, float* dx, float* g0, int b, long L,
                                int E, int C, float beta, int n_it, void* ws, size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(xn && cents && dx && g0 && ws && b > 0 && L > 0 && C >= 2 && C <= 4 && beta >= 0.f && n_it >= 0 && (n_it == 0 || dens));
+    AMS_REQUIRE(xn && cents && dx && g0 && ws && b > 0 && L > 0 && C >= 2 && C <= 6 && beta >= 0.f && n_it >= 0 && (n_it == 0 || dens));
     AMS_REQUIRE((!inv || seed) && (!inv0 || inv));  // with a Jacobian applied to dx the caller can no longer add g0 to it
     if (ws_bytes < ams_kmeans_soft_bwd_workspace_bytes(b, L, E, C, n_it)) return AMS_E_WORKSPACE_TOO_SMALL;
     KsArgs a{};
@@ -483,7 +485,7 @@ ams_status ams_kmeans_soft_bwd(const float* xn, const float* w, const float* w_f
     const size_t CE = (size_t)C * E;
     char* p = (char*)ws;
     a.part = (float*)p; p += ks_align((size_t)b * a.nG * (CE + C) * 4);
-    a.rec = (float*)p; p += ks_align((size_t)b * (n_it + 1) * (2 * CE + 8) * 4);
+    a.rec = (float*)p; p += ks_align((size_t)b * (n_it + 1) * (2 * CE + 2 * ks_pad(C)) * 4);
     a.G = (float*)p; p += ks_align((size_t)(n_it + 1) * b * CE * 4);
     a.ticket = (unsigned*)p;
     // (the partial sums above are laid out for the chunk count this launch uses, which may be below the one the size query assumed: the
@@ -496,6 +498,10 @@ ams_status ams_kmeans_soft_bwd(const float* xn, const float* w, const float* w_f
     if (E == 8 && C == 2) return ks_run<8, 2>(a, st);
     if (E == 8 && C == 3) return ks_run<8, 3>(a, st);
     if (E == 20 && C == 2) return ks_run<20, 2>(a, st);
+    if (E == 40 && C == 5) return ks_run<40, 5>(a, st);
+    if (E == 40 && C == 6) return ks_run<40, 6>(a, st);
+    if (E == 8 && C == 5) return ks_run<8, 5>(a, st);
+    if (E == 8 && C == 6) return ks_run<8, 6>(a, st);
     return AMS_E_INVALID_ARG;
 }
 

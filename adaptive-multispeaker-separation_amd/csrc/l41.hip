@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int MAXS = 4;
+constexpr int MAXS_ALL = 6;       // speakers (kernels are instantiated for MAXS = 4 -- every S <= 4, as ever -- and MAXS = 6 for S = 5, 6)
 constexpr int MAXK = 16;          // negatives per set
 constexpr int MAXN = 32;          // NSEL * K
 
@@ -32,7 +32,8 @@ struct NegArgs {
 // l2-normalise pass before the loss (read + write of the embedding tensor) and none after it (two reads + one write): 0.9 ms of a 9.5 ms
 // cfg5 step.  VEC: 16-byte global accesses and LDS rows (E % 4 == 0, 16-byte aligned tensors): the 4-byte form ran the backward at
 // 2.3 TB/s.
-template <int E_, bool BWD, bool NEG, bool FROM_U, bool VEC>
+// MAXS: rows of the per-point dz table in LDS (and its running sums): 4 is one float4 per point, 6 is read as scalars.
+template <int E_, bool BWD, bool NEG, bool FROM_U, bool VEC, int MAXS>
 __global__ __launch_bounds__(256) void l41_kernel(const float* __restrict__ emb, const float* __restrict__ y,
                                                   const float* __restrict__ vs, const float* __restrict__ upstream,
                                                   float* __restrict__ part, float* __restrict__ demb, float* __restrict__ dvs_part,
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void l41_kernel(const float* __restrict__ emb,
         for (int i = tid; i < na.NSEL * na.K * E_; i += 256) sneg[i] = na.negs[(long)b * na.NSEL * na.K * E_ + i];
     __syncthreads();
     float cost = 0.f;
-    float dz[MAXS] = {0.f, 0.f, 0.f, 0.f};
+    float dz[MAXS] = {};
     float v[E_];
     int sel = 0;
     float inv_u = 1.0f;
@@ -169,17 +170,28 @@ __global__ __launch_bounds__(256) void l41_kernel(const float* __restrict__ emb,
         if (part < NPART) {
             const int per = (256 + NPART - 1) / NPART;
             const int pa = part * per, pb = min(npts, pa + per);
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            for (int p = pa; p < pb; ++p) {
-                const float vv = tile[p * LD + eo];
-                const float4 dz4 = *reinterpret_cast<const float4*>(&sdzs[p * MAXS]);
-                a0 += dz4.x * vv; a1 += dz4.y * vv; a2 += dz4.z * vv; a3 += dz4.w * vv;
-            }
             float* const r = &red[part * (MAXS * E_)];
-            r[eo] = a0; r[E_ + eo] = a1; r[2 * E_ + eo] = a2; r[3 * E_ + eo] = a3;
+            if constexpr (MAXS == 4) {
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                for (int p = pa; p < pb; ++p) {
+                    const float vv = tile[p * LD + eo];
+                    const float4 dz4 = *reinterpret_cast<const float4*>(&sdzs[p * MAXS]);
+                    a0 += dz4.x * vv; a1 += dz4.y * vv; a2 += dz4.z * vv; a3 += dz4.w * vv;
+                }
+                r[eo] = a0; r[E_ + eo] = a1; r[2 * E_ + eo] = a2; r[3 * E_ + eo] = a3;
+            } else {
+                float as[MAXS] = {};
+                for (int p = pa; p < pb; ++p) {
+                    const float vv = tile[p * LD + eo];
+#pragma unroll
+                    for (int s = 0; s < MAXS; ++s) as[s] += sdzs[p * MAXS + s] * vv;
+                }
+#pragma unroll
+                for (int s = 0; s < MAXS; ++s) r[s * E_ + eo] = as[s];
+            }
         }
         __syncthreads();
-        if (tid < S * E_) {                                                      // (S * E <= 160: one output per thread, kept in a register)
+        if (tid < S * E_) {                                                      // (S * E <= 240: one output per thread, kept in a register)
 #pragma unroll
             for (int q = 0; q < NPART; ++q) dvs_tot += red[q * (MAXS * E_) + tid];
         }
@@ -256,7 +268,9 @@ size_t ams_l41_workspace_bytes(int B, long TF, int E, int S) {
     return sizeof(float) * (size_t)B * nblk * ((S * E > 1 ? S * E : 1) + 1);          // + one maximum per block (backward: amax_out)
 }
 
-#define AMS_L41_CASE(EE, BWD, NEG, U, V, ...) hipLaunchKernelGGL((l41_kernel<EE, BWD, NEG, U, V>), grid, dim3(256), 0, st, __VA_ARGS__)
+#define AMS_L41_CASE(EE, BWD, NEG, U, V, ...)                                                                 \
+    do { if (S <= 4) hipLaunchKernelGGL((l41_kernel<EE, BWD, NEG, U, V, 4>), grid, dim3(256), 0, st, __VA_ARGS__);  \
+         else hipLaunchKernelGGL((l41_kernel<EE, BWD, NEG, U, V, 6>), grid, dim3(256), 0, st, __VA_ARGS__); } while (0)
 #define AMS_L41_E(EE, BWD, NEG, ...)                                                                          \
     if (EE % 4 == 0 && vec) { if (from_u) AMS_L41_CASE(EE, BWD, NEG, true, (EE % 4 == 0), __VA_ARGS__); else AMS_L41_CASE(EE, BWD, NEG, false, (EE % 4 == 0), __VA_ARGS__); } \
     else { if (from_u) AMS_L41_CASE(EE, BWD, NEG, true, false, __VA_ARGS__); else AMS_L41_CASE(EE, BWD, NEG, false, false, __VA_ARGS__); }
@@ -273,12 +287,12 @@ size_t ams_l41_workspace_bytes(int B, long TF, int E, int S) {
     }
 inline bool l41_vec(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
-// emb [B,TF,E], y [B,TF,S] (+1/-1), vspk [B,S,E] (already gathered / normalised) -> cost[0]
+// emb [B,TF,E], y [B,TF,S] (+1/-1), vspk [B,S,E] (already gathered / normalised) -> cost[0].  S <= 6, S * E <= 256 (all four entry points).
 // emb_is_u (all four entry points): emb is the network output BEFORE tf.nn.l2_normalize over E (models/L41.py:43): it is normalised
 // inside the pass, and the backward returns the gradient w.r.t. that un-normalised tensor.
 ams_status ams_l41_loss_fwd(const float* emb, const float* y, const float* vspk, float* cost, int B, long TF, int E, int S, int emb_is_u,
                             void* ws, size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(emb && y && vspk && cost && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS);
+    AMS_REQUIRE(emb && y && vspk && cost && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS_ALL);
     if (ws_bytes < ams_l41_workspace_bytes(B, TF, E, S)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ceil_div(TF, 256);
@@ -294,7 +308,7 @@ ams_status ams_l41_loss_fwd(const float* emb, const float* y, const float* vspk,
 // amax_out (optional, both backward entry points): one float that receives max |demb| of this launch
 ams_status ams_l41_loss_bwd(const float* emb, const float* y, const float* vspk, const float* upstream, float* demb, float* dvspk,
                             float* amax_out, int B, long TF, int E, int S, int emb_is_u, void* ws, size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(emb && y && vspk && upstream && demb && dvspk && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS);
+    AMS_REQUIRE(emb && y && vspk && upstream && demb && dvspk && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS_ALL);
     if (ws_bytes < ams_l41_workspace_bytes(B, TF, E, S)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ceil_div(TF, 256);
@@ -316,7 +330,7 @@ size_t ams_l41_ns_workspace_bytes(int B, long TF, int E, int S, int NSEL, int K)
 
 ams_status ams_l41_loss_ns_fwd(const float* emb, const float* y, const float* vspk, const float* negs, float* cost, int B, long TF, int E,
                                int S, int NSEL, int K, float ns_rate, int emb_is_u, void* ws, size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(emb && y && vspk && negs && cost && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS);
+    AMS_REQUIRE(emb && y && vspk && negs && cost && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS_ALL);
     AMS_REQUIRE((NSEL == 1 || NSEL == S) && K > 0 && K <= MAXK && NSEL * K <= MAXN);
     if (ws_bytes < ams_l41_ns_workspace_bytes(B, TF, E, S, NSEL, K)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
@@ -334,7 +348,7 @@ ams_status ams_l41_loss_ns_fwd(const float* emb, const float* y, const float* vs
 ams_status ams_l41_loss_ns_bwd(const float* emb, const float* y, const float* vspk, const float* negs, const float* upstream, float* demb,
                                float* dvspk, float* dnegs, float* amax_out, int B, long TF, int E, int S, int NSEL, int K, float ns_rate,
                                int emb_is_u, void* ws, size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(emb && y && vspk && negs && upstream && demb && dvspk && dnegs && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS);
+    AMS_REQUIRE(emb && y && vspk && negs && upstream && demb && dvspk && dnegs && ws && B > 0 && TF > 0 && S > 0 && S <= MAXS_ALL);
     AMS_REQUIRE((NSEL == 1 || NSEL == S) && K > 0 && K <= MAXK && NSEL * K <= MAXN);
     if (ws_bytes < ams_l41_ns_workspace_bytes(B, TF, E, S, NSEL, K)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;

@@ -31,10 +31,11 @@ __global__ void overlap_add_kernel(const float* __restrict__ fr, float* __restri
 
 // stats layout per utterance b (floats), NS = 2 S^2 + 3 S + 1:
 //   D[S*S] (D[s*S+s'] = <t_s, a_s'>) | Q[S*S] (|t_s - a_s'|^2) | Na[S] | Nt[S] | Tm[S] (<t_s, mix>) | Nm[1]
+// MAXS = 4 is the kernel every recipe up to four speakers has always run (41 running sums per lane); MAXS = 6 serves S = 5, 6 with 91.
+template <int MAXS>
 __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict__ tgt, const float* __restrict__ est,
                                                          const float* __restrict__ mix, float* __restrict__ part, int S, long L,
                                                          int nchunk, long chunk) {
-    constexpr int MAXS = 4;
     constexpr int MAXNS = 2 * MAXS * MAXS + 3 * MAXS + 1;
     __shared__ float sm[4][MAXNS];
     const int b = blockIdx.y, c = blockIdx.x;
@@ -219,6 +220,50 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
     return r;
 }
 
+// One permutation's cost, formed the same way wherever it is formed (the search below, the combine kernel): terms that two
+// permutations share are shared bit for bit.
+__device__ __forceinline__ float perm_cost(const float* q, const int* perm, int S, float cl, float cs) {
+    float c = 0.f;
+    for (int s = 0; s < S; ++s) c += q[s * S + perm[s]] * cl;
+    return c * cs;
+}
+
+// The permutation search for S = 5, 6 (120 / 720 permutations): one workgroup per utterance.  The utterance's S x S slice of Q sits in
+// LDS, lane t owns permutations t, t + 256, t + 512 of the lexicographic table (ascending, so a lane's strict `<` keeps its lowest
+// index), and the workgroup meets in a halving tree whose order is (cost, index): the minimum cost, and among equal costs the lowest
+// permutation index -- the first-minimum rule of tf.reduce_min / np.argmin.  Only pbest is written: pair_combine_fwd_kernel<true>
+// forms the winner's cost again (perm_cost: same bits) and takes the batch mean in its fixed order.
+__global__ __launch_bounds__(256) void pair_search_kernel(const float* __restrict__ st, const int* __restrict__ perms,
+                                                          int* __restrict__ pbest, int S, int P, float cl, float cs) {
+    __shared__ float q[36];
+    __shared__ float sc[256];
+    __shared__ int sp[256];
+    const int SS = S * S, NS = 2 * SS + 3 * S + 1, tid = threadIdx.x, b = blockIdx.x;
+    if (tid < SS) q[tid] = st[(long)b * NS + SS + tid];
+    __syncthreads();
+    float best = 0.f;
+    int bp = P;                                                    // P: this lane owns no permutation
+    for (int p = tid; p < P; p += 256) {
+        const float c = perm_cost(q, perms + (long)p * S, S, cl, cs);
+        if (bp == P || c < best) { best = c; bp = p; }
+    }
+    sc[tid] = best;
+    sp[tid] = bp;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if (tid < h) {
+            const float c2 = sc[tid + h];
+            const int p2 = sp[tid + h], p1 = sp[tid];
+            // (sp == P marks a lane that owns no permutation: only where P < 256)
+            if (p2 < P && (p1 == P || c2 < sc[tid] || (c2 == sc[tid] && p2 < p1))) { sc[tid] = c2; sp[tid] = p2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) pbest[b] = sp[0];
+}
+
+// PRESEARCHED: pbest was written by pair_search_kernel (S > 4); false is the kernel of S <= 4, which walks the permutations itself
+template <bool PRESEARCHED>
 __global__ __launch_bounds__(256) void pair_combine_fwd_kernel(const float* __restrict__ st, const float* __restrict__ D2,
                                                                const int* __restrict__ perms, float* __restrict__ out,
                                                                int* __restrict__ pbest, int* __restrict__ jbest, int B, int S, int P,
@@ -244,14 +289,18 @@ __global__ __launch_bounds__(256) void pair_combine_fwd_kernel(const float* __re
     for (int b = tid; b < B; b += 256) {
         const float* q = st + (long)b * NS + SS;
         float best = 0.f;
-        int bp = 0;
-        for (int p = 0; p < P; ++p) {
-            float c = 0.f;
-            for (int s = 0; s < S; ++s) c += q[s * S + perms[p * S + s]] * cl;
-            c *= cs;
-            if (p == 0 || c < best) { best = c; bp = p; }
+        if constexpr (PRESEARCHED) {
+            best = perm_cost(q, perms + (long)pbest[b] * S, S, cl, cs);
+        } else {
+            int bp = 0;
+            for (int p = 0; p < P; ++p) {
+                float c = 0.f;
+                for (int s = 0; s < S; ++s) c += q[s * S + perms[p * S + s]] * cl;
+                c *= cs;
+                if (p == 0 || c < best) { best = c; bp = p; }
+            }
+            pbest[b] = bp;
         }
-        pbest[b] = bp;
         a0 += best;
     }
     if (mode == PC_ADAPT) {
@@ -346,19 +395,20 @@ size_t ams_pair_stats_workspace_bytes(int B, int S, long L) {
 
 ams_status ams_pair_stats_fwd(const float* target, const float* est, const float* mix, float* stats, int B, int S, long L, void* ws,
                               size_t ws_bytes, void* stream) {
-    AMS_REQUIRE(target && est && stats && ws && B > 0 && S > 0 && S <= 4 && L > 0);
+    AMS_REQUIRE(target && est && stats && ws && B > 0 && S > 0 && S <= 6 && L > 0);
     const int NS = 2 * S * S + 3 * S + 1;
     const int nchunk = ceil_div(L, 4096);
     if (ws_bytes < (size_t)B * nchunk * NS * sizeof(float)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(pair_stats_kernel, dim3(nchunk, B), dim3(256), 0, st, target, est, mix, (float*)ws, S, L, nchunk, (long)4096);
+    if (S <= 4) hipLaunchKernelGGL(pair_stats_kernel<4>, dim3(nchunk, B), dim3(256), 0, st, target, est, mix, (float*)ws, S, L, nchunk, (long)4096);
+    else hipLaunchKernelGGL(pair_stats_kernel<6>, dim3(nchunk, B), dim3(256), 0, st, target, est, mix, (float*)ws, S, L, nchunk, (long)4096);
     hipLaunchKernelGGL(pair_stats_final_kernel, dim3(ceil_div(B * NS, 256)), dim3(256), 0, st, (const float*)ws, stats, NS, nchunk, B);
     return ams_check_launch();
 }
 
 ams_status ams_pair_stats_bwd(const float* target, const float* est, const float* gstats, float* dest, int B, int S, long L,
                               void* stream) {
-    AMS_REQUIRE(target && est && gstats && dest && B > 0 && S > 0 && S <= 4 && L > 0);
+    AMS_REQUIRE(target && est && gstats && dest && B > 0 && S > 0 && S <= 6 && L > 0);
     long n = (long)B * S * L;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 4096) blocks = 4096;
@@ -414,18 +464,25 @@ ams_status ams_overlap_metric_bwd(const float* y, const float* upstream, float* 
 // the forward pass and read by the backward pass.  gD2 may be NULL unless mode == 2.
 ams_status ams_pair_combine_fwd(const float* stats, const float* D2, const int* perms, float* out, int* pbest, int* jbest, int B, int S,
                                 int P, int mode, float cl, float cs, void* stream) {
-    AMS_REQUIRE(stats && out && B > 0 && S > 0 && S <= 4 && mode >= 0 && mode <= 2);
+    AMS_REQUIRE(stats && out && B > 0 && S > 0 && S <= 6 && mode >= 0 && mode <= 2);
     AMS_REQUIRE(mode == PC_PRETRAIN || (perms && pbest && P > 0));
     AMS_REQUIRE(mode != PC_ADAPT || (D2 && jbest));
-    hipLaunchKernelGGL(pair_combine_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, D2, perms, out, pbest, jbest, B, S, P,
-                       mode, cl, cs);
+    if (S > 4 && mode != PC_PRETRAIN) {
+        // S = 5, 6: the search runs one workgroup per utterance (pair_search_kernel), the combine kernel reads its pbest
+        hipLaunchKernelGGL(pair_search_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, stats, perms, pbest, S, P, cl, cs);
+        hipLaunchKernelGGL(pair_combine_fwd_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, D2, perms, out, pbest, jbest,
+                           B, S, P, mode, cl, cs);
+        return ams_check_launch();
+    }
+    hipLaunchKernelGGL(pair_combine_fwd_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, D2, perms, out, pbest, jbest, B,
+                       S, P, mode, cl, cs);
     return ams_check_launch();
 }
 
 ams_status ams_pair_combine_bwd(const float* stats, const float* D2, const int* perms, const float* gout, const int* pbest,
                                 const int* jbest, float* gstats, float* gD2, int B, int S, int P, int mode, float cl, float cs,
                                 void* stream) {
-    AMS_REQUIRE(stats && gout && gstats && B > 0 && S > 0 && S <= 4 && mode >= 0 && mode <= 2);
+    AMS_REQUIRE(stats && gout && gstats && B > 0 && S > 0 && S <= 6 && mode >= 0 && mode <= 2);
     AMS_REQUIRE(mode == PC_PRETRAIN || (perms && pbest && P > 0));
     AMS_REQUIRE(mode != PC_ADAPT || (D2 && jbest && gD2));
     hipLaunchKernelGGL(pair_combine_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, D2, perms, gout, pbest, jbest, gstats,

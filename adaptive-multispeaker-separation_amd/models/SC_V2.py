@@ -16,6 +16,11 @@ class L41ModelV2(Separator):
         kwargs['mask_a'] = 1.0
         kwargs['mask_b'] = -1.0
 
+        if kwargs.get('nb_speakers', 0) > 4:
+            # the attractor / reconstruction kernels (csrc/danet.hip) keep one float4 of masks per bin: four speakers
+            raise ValueError('--nb_speakers %d: L41ModelV2 (DANet-SCE) supports at most 4 speakers -- its attractor and reconstruction '
+                             'kernels hold four masks per bin; the other separators take up to 6' % kwargs['nb_speakers'])
+
         super(L41ModelV2, self).__init__(graph, **kwargs)
 
         if self.loss_with_silence and self.add_dilated and not self.plugged:

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 8
+#define AMS_ABI_VERSION 9
 
 typedef int32_t ams_status;
 #define AMS_OK 0
@@ -419,7 +419,8 @@ ams_status ams_frames_matmul_bwd_filter(const float* x, const float* dy, float* 
 ams_status ams_overlap_add(const float* frames, float* out, int R, int T, int W, int L, int hop, int pad_left, void* stream);
 
 /* ---- K22/K23 waveform statistics for SDR / L2 / PIT costs   models/adapt.py:321-372,404-431; network.py:196-221,662-724
- * stats per utterance: D[S*S] (<t_s,a_s'>) | Na[S] | Nt[S] | Tm[S] (<t_s,mix>) | Nm[1];  mix may be NULL ---- */
+ * stats per utterance: D[S*S] (<t_s,a_s'>) | Na[S] | Nt[S] | Tm[S] (<t_s,mix>) | Nm[1];  mix may be NULL.
+ * 1 <= S <= 6 (ABI 9; was 4), here and in ams_pair_combine_*: S <= 4 runs the kernels it always ran, S = 5, 6 kernels of their own ---- */
 size_t ams_pair_stats_workspace_bytes(int B, int S, long L);
 ams_status ams_pair_stats_fwd(const float* target, const float* est, const float* mix, float* stats, int B, int S, long L, void* ws,
                               size_t ws_bytes, void* stream);
@@ -430,7 +431,10 @@ ams_status ams_pair_stats_bwd(const float* target, const float* est, const float
  * mode 1 PIT squared error -> out[0] = mean_b min_p red_s(Q[b,s,p(s)] * cl), red = sum (cs = 1) or mean (cs = 1/S);
  * mode 2 Adapt.cost non-pretraining branch -> out = (mean_b min_p sum_s Q/L, mean_i sum_s min_j Nt[i,s] Na[j,s]/(D2[s,i,j]^2+1e-12)),
  * D2 [S,B,B] the cross-batch dot products (adapt.py:361-365).  perms [P,S] int32, lexicographic; pbest [B], jbest [B,S] int32
- * carry the arg-minima from the forward to the backward call; gstats [B,NS] / gD2 [S,B,B] are fully overwritten. */
+ * carry the arg-minima from the forward to the backward call; gstats [B,NS] / gD2 [S,B,B] are fully overwritten.
+ * S = 5, 6 (modes 1, 2): the forward call is two launches -- a permutation search of one workgroup per utterance, whose lanes own
+ * permutations and meet in a tree ordered by (cost, index): the minimum, and the LOWEST index among equal costs, like the sequential
+ * search of S <= 4 -- then the combine launch. */
 ams_status ams_pair_combine_fwd(const float* stats, const float* D2, const int* perms, float* out, int* pbest, int* jbest, int B, int S,
                                 int P, int mode, float cl, float cs, void* stream);
 ams_status ams_pair_combine_bwd(const float* stats, const float* D2, const int* perms, const float* gout, const int* pbest,
@@ -456,7 +460,8 @@ ams_status ams_cplx_apply_bwd(const float* dz, const float* phasor, float* dsep,
  * emb_is_u (all four entry points): 0 = emb holds the embeddings the loss is defined on; 1 = emb is the network output BEFORE
  * tf.nn.l2_normalize over E (models/L41.py:43 Normalize(3), utils/ops.py:323): every point is normalised in registers inside the pass
  * and the backward returns the gradient w.r.t. that un-normalised tensor (the normalise Jacobian applied before the store) -- K13
- * fused into K15 as it is into K14 (ams_dpcl_loss_fwd_u): no l2-normalise pass before the loss and none after it. */
+ * fused into K15 as it is into K14 (ams_dpcl_loss_fwd_u): no l2-normalise pass before the loss and none after it.
+ * 1 <= S <= 6 (ABI 9; was 4), E in {3, 4, 8, 16, 20, 32, 40}: all four entry points. */
 size_t ams_l41_workspace_bytes(int B, long TF, int E, int S);
 ams_status ams_l41_loss_fwd(const float* emb, const float* y, const float* vspk, float* cost, int B, long TF, int E, int S, int emb_is_u,
                             void* ws, size_t ws_bytes, void* stream);
@@ -499,7 +504,9 @@ ams_status ams_danet_recon_bwd(const float* y, const float* x_sil, float sil_thr
 
 /* ---- K16-K19 batched k-means   models/Kmeans_2.py:40-188 ----
  * xn [b,L,E] normalised input (ams_kmeans_normalize); rows r = b_idx*tries + try; centroids [b*tries, C, E];
- * w [b,L] silence weights or NULL; beta < 0 => hard assignment; w_mod_b reproduces the reference's tile order. */
+ * w [b,L] silence weights or NULL; beta < 0 => hard assignment; w_mod_b reproduces the reference's tile order.
+ * ams_kmeans_iterate / ams_kmeans_assign: (E, C) in {40, 8} x {2 .. 6} or {20} x {2, 3} (ABI 9: C = 5, 6);
+ * ams_kmeans_soft_bwd: (40, 2 .. 6), (8, 2 | 3 | 5 | 6), (20, 2) (ABI 9: C = 5, 6). */
 ams_status ams_kmeans_normalize(const float* x, float* xn, long nrows, int E, void* stream);
 size_t ams_kmeans_workspace_bytes(int R, long L, int E, int C);
 ams_status ams_kmeans_init(const float* xn, const int32_t* init_idx, float* centroids, int b, int tries, long L, int E, int C,
