@@ -66,14 +66,14 @@ class _Overlap(object):
             self.n_cap += 1
         ops.LDS_PAD[0] = pad if on else 0               # handed to every product launched until the next cap() (include/ams.h: lds_pad)
 
-    def capped(self, kind='dense', on=True):
+    def capped(self, kind='dense'):
         """with OVERLAP.capped('lstm'): ...  -- the products inside carry the residency cap, and the cap is lifted again whatever
         happens inside (a product that raises must not leave every later critical-path product capped)."""
         ov = self
 
         class _Cap(object):
             def __enter__(self_):
-                ov.cap(on, kind)
+                ov.cap(True, kind)
 
             def __exit__(self_, *exc):
                 ov.cap(False)
@@ -143,11 +143,7 @@ class FrontConv(Function):
 
 
 import os as _os
-_ORDER = int(_os.environ.get('AMS_OVERLAP_ORDER', '2'))
-# dense layer backward: 0 = dX first, dW capped beside the next recurrence (9.30 k mixtures/s); 1 = dW || dX uncapped (9.05 k);
-# 2 = dW alone, then dX (8.97 k) -- measured on the B=64 step, kept as a tuning aid
-_DENSE_MODE = int(_os.environ.get('AMS_DENSE_MODE', '0'))
-_L1_TAIL = int(_os.environ.get('AMS_L1_TAIL', '0'))
+# dense layer backward: dX first, dW capped beside the next recurrence (9.30 k mixtures/s; dW || dX uncapped 9.05 k; dW alone, then dX 8.97 k)
 # column blocks (in 256-column tiles) of the dense weight gradient: the first runs beside the top BPTT ring, the others one per later window
 _DW_SPLIT = [int(v) for v in _os.environ.get('AMS_DW_SPLIT', '24,12,4').split(',') if v]
 
@@ -198,22 +194,13 @@ class BLSTMLayer(Function):
                 az = ops.amax_of(G)                              # G now holds dZ; the ring left its bound, the step kernels do not
                 am_dx = (az, ctx.amax[1])
                 am_w = (ctx.amax[0], ops.amax_one(G.device), az)
-            dx = None
-            if _ORDER >= 2 and need_dx:
-                dx = ops.blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=am_dx)
+            dx = ops.blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=am_dx) if need_dx else None
             s = OVERLAP.fork(x, out, G, *([dbpart] if dbpart is not None else []))
             if not need_dx:
                 # first layer: no recurrence follows -- both streams work on the weight gradients, uncapped
-                if _L1_TAIL == 0:
-                    with torch.cuda.stream(s):
-                        ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='u', amax=am_w)
-                    ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='wx', dbpart=dbpart, amax=am_w)
-                elif _L1_TAIL == 1:
-                    ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='wx', dbpart=dbpart, amax=am_w)
+                with torch.cuda.stream(s):
                     ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='u', amax=am_w)
-                else:
-                    ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='u', amax=am_w)
-                    ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='wx', dbpart=dbpart, amax=am_w)
+                ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='wx', dbpart=dbpart, amax=am_w)
                 return None, None, None, None, None, None
             with torch.cuda.stream(s):
                 with OVERLAP.capped('lstm'):
@@ -224,8 +211,6 @@ class BLSTMLayer(Function):
                     ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='u', amax=am_w)
                 OVERLAP.ready(Kf, bf, Kb, bb)
                 OVERLAP.flush(1)                    # one deferred column block of the dense weight gradient per window
-            if dx is None and need_dx:
-                dx = ops.blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=am_dx)
             return dx, None, None, None, None, None
         dx, dKf, dbf, dKb, dbb = ops.blstm_bwd(x, Kf, Kb, out, G, cst, _c(dout), need_dx=need_dx,
                                                 amax_u=ctx.amax[1] if ctx.amax is not None else None)
@@ -283,18 +268,16 @@ class Dense(Function):
             adu = ops.amax_of(du2)                               # the loss kernel that wrote dU left its bound (ops.dpcl_loss_bwd_u)
             am_dx, am_dw = (adu, ctx.amax[1]), (ctx.amax[0], adu)
         if OVERLAP.usable(W, b) and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            dx = None
-            if _DENSE_MODE == 0 and _ORDER >= 1 and ctx.needs_input_grad[0]:
-                dx = ops.backward_product(du2, W, am_dx, W).view(x.shape)
+            dx = ops.backward_product(du2, W, am_dx, W).view(x.shape) if ctx.needs_input_grad[0] else None
             s = OVERLAP.fork(x2, du2)
             Nw = W.shape[1]
-            cuts = _dw_cuts(Nw) if (_DENSE_MODE == 0 and ctx.needs_input_grad[0] and W.grad.stride(0) == Nw) else [(0, Nw)]
+            cuts = _dw_cuts(Nw) if (ctx.needs_input_grad[0] and W.grad.stride(0) == Nw) else [(0, Nw)]
 
             def piece(n0, n1):
                 # dW[:, n0:n1] = x^T dU[:, n0:n1] and db[n0:n1] = colsum from ONE pass over those columns of dU
                 Wg = W.grad if (n0, n1) == (0, Nw) else W.grad[:, n0:n1]
                 dus = du2 if (n0, n1) == (0, Nw) else du2[:, n0:n1]
-                with OVERLAP.capped('dense', _DENSE_MODE == 0):
+                with OVERLAP.capped('dense'):
                     fused = ops.gemm_at_b_colsum(x2, dus, Wg, b.grad[n0:n1], accumulate=True, amax=am_dw, ldc=W.grad.stride(0))
                     if not fused:
                         ops.gemm(x2, dus, transA=True, out=Wg, accumulate=True, amax=am_dw, M=x2.shape[1], N=n1 - n0, K=x2.shape[0],
@@ -311,12 +294,6 @@ class Dense(Function):
                 OVERLAP.defer(lambda c=c, last=last: (piece(*c), OVERLAP.ready(W, b) if last else None))
             if len(cuts) == 1:
                 OVERLAP.ready(W, b)
-            if _DENSE_MODE == 2 and ctx.needs_input_grad[0]:
-                # the weight-gradient product runs FIRST and alone (uncapped), dX after it: nothing of the dense layer is left
-                # on the side stream when the recurrence below starts
-                torch.cuda.current_stream().wait_stream(s)
-            if dx is None and ctx.needs_input_grad[0]:
-                dx = ops.backward_product(du2, W, am_dx, W).view(x.shape)
             return dx, None, None
         dx = ops.backward_product(du2, W, am_dx, W).view(x.shape) if ctx.needs_input_grad[0] else None
         dW = ops.gemm(x2, du2, transA=True, amax=am_dw) if ctx.needs_input_grad[1] else None

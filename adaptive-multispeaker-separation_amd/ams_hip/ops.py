@@ -122,6 +122,7 @@ def _ws(nbytes, like):
 
 _SK = {}
 SK = _os.environ.get('AMS_GEMM_SK', '1') != '0'
+NOVEC = _os.environ.get('AMS_GEMM_NOVEC') is not None         # the library's products take the dword-fetch f32 kernel
 
 
 def _sk(like):
@@ -806,7 +807,7 @@ def gemm_at_b_colsum(A, B, out, bsum, accumulate=True, amax=None, ldc=None):
     ldc = out.stride(0) if ldc is None else ldc
     ok = (M % 4 == 0 and N % 4 == 0 and A.stride(0) % 4 == 0 and B.stride(0) % 4 == 0 and A.stride(1) == 1 and B.stride(1) == 1
           and out.stride(-1) == 1 and bsum.stride(-1) == 1 and bsum.data_ptr() % 16 == 0
-          and all(t.data_ptr() % 16 == 0 for t in (A, B)) and _os.environ.get('AMS_GEMM_NOVEC') is None)
+          and all(t.data_ptr() % 16 == 0 for t in (A, B)) and not NOVEC)
     if not ok:
         return False
     lib = load()

@@ -239,13 +239,11 @@ struct GramFinish {
     int B;
 };
 
-template <int NT, int EC, int SC>                  // EC / SC: compile-time E / S (0 = use the run-time value; EC != 0 implies 16-byte rows)
+template <int NT>
 __global__ __launch_bounds__(256) void dpcl_gram_u_kernel(const float* __restrict__ U, const float* __restrict__ Y,
                                                           const float* __restrict__ cntp, float* __restrict__ inv_out,
-                                                          float* __restrict__ V_out, float* __restrict__ part, long TF, int E_rt,
-                                                          int S_rt, int nchunk, GramFinish fin) {
-    const int E = EC ? EC : E_rt;
-    const int S = SC ? SC : S_rt;
+                                                          float* __restrict__ V_out, float* __restrict__ part, long TF, int E,
+                                                          int S, int nchunk, GramFinish fin) {
     constexpr int Z = NT * 16;
     constexpr int ZP = Z + 4;                       // row pitch: 16-byte aligned rows, 16 lanes x 16 B cover all banks
     constexpr int PTS = NT <= 3 ? AMS_DPCL_PTS : 128;        // points staged per iteration
@@ -269,7 +267,7 @@ __global__ __launch_bounds__(256) void dpcl_gram_u_kernel(const float* __restric
     const long p_begin = (long)c * UCHUNK, p_end = min(TF, p_begin + UCHUNK);
     const float* Ub = U + (long)b * TF * E;
     const float* Yb = Y + (long)b * TF * S;
-    const bool vec = EC ? true : ((E % 4 == 0) && (((uintptr_t)U & 15) == 0));      // EC path: the launcher checked alignment
+    const bool vec = (E % 4 == 0) && (((uintptr_t)U & 15) == 0);
     const int nvec = PTS * E / 4;                   // 16-byte groups per full slab (vec path)
 
     float4 pre[NV];
@@ -801,14 +799,12 @@ __global__ __launch_bounds__(256) void dpcl_bwd_kernel(const float* __restrict__
 // on the fly.  The l2-normalise Jacobian (a 16-lane dot per point) is applied on the accumulators and dU goes back
 // through LDS so global traffic is 16-byte coalesced both ways; slab i+1 is fetched while slab i is in the MFMA phase.
 // Algorithmic HBM bytes per utterance: TF*(2E+S+1)*4.
-template <int NT, int EC, int SC>                  // EC / SC: compile-time E / S (0 = run-time; EC != 0 implies 16-byte rows)
+template <int NT>
 __global__ __launch_bounds__(256, 2) void dpcl_bwd_u_kernel(const float* __restrict__ U, const float* __restrict__ Y,
                                                          const float* __restrict__ cntp, const float* __restrict__ mats,
                                                          const float* __restrict__ inv, const float* __restrict__ upstream,
-                                                         float* __restrict__ dU, long TF, int E_rt, int S_rt, unsigned* __restrict__ amax_out) {
-    const int E = EC ? EC : E_rt;
+                                                         float* __restrict__ dU, long TF, int E, int S, unsigned* __restrict__ amax_out) {
     float amax_f = 0.f;                             // max |dU| seen by this lane (v_max3_f32 with |.| modifiers)
-    const int S = SC ? SC : S_rt;
     constexpr int Z = NT * 16, ZP = Z + 4, KT = Z / 4;
     constexpr int PTS = NT <= 3 ? AMS_DPCL_PTS : 128;
     constexpr int NV = PTS * Z / 4 / 256;
@@ -847,7 +843,7 @@ __global__ __launch_bounds__(256, 2) void dpcl_bwd_u_kernel(const float* __restr
     const float* Yb = Y + (long)b * TF * S;
     const float* ib = inv + (long)b * TF;
     float* dUb = dU + (long)b * TF * E;
-    const bool vec = EC ? true : ((E % 4 == 0) && (((uintptr_t)U & 15) == 0) && (((uintptr_t)dU & 15) == 0));
+    const bool vec = (E % 4 == 0) && (((uintptr_t)U & 15) == 0) && (((uintptr_t)dU & 15) == 0);
     const int nvec = PTS * E / 4;
 
     float4 pre[NV];
@@ -1230,18 +1226,6 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
     }
 }
 
-// AMS_DPCL_GRAM_F16=0 (read once): the fused forward keeps its Gram on v_mfma_f32_16x16x4_f32 (A/B runs; the tests hold both)
-inline bool dpcl_gram_f16() {
-    static const bool v = !(getenv("AMS_DPCL_GRAM_F16") && atoi(getenv("AMS_DPCL_GRAM_F16")) == 0);
-    return v;
-}
-
-// AMS_DPCL_LDS=1 (read once): the LDS-staged passes of round 2 also where the direct ones apply (A/B runs, tests hold both)
-inline bool dpcl_direct() {
-    static const bool v = !(getenv("AMS_DPCL_LDS") && atoi(getenv("AMS_DPCL_LDS")) != 0);
-    return v;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1355,18 +1339,16 @@ ams_status ams_dpcl_loss_fwd_u(const float* U, const float* Y, float* inv, float
     const GramFinish fin = {per_utt, mats, out, slot + 1, slot, B};
     dim3 grid(nchunk, B);
     switch (NT) {
-        case 1: hipLaunchKernelGGL((dpcl_gram_u_kernel<1, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
-        case 2: hipLaunchKernelGGL((dpcl_gram_u_kernel<2, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
+        case 1: hipLaunchKernelGGL((dpcl_gram_u_kernel<1>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
+        case 2: hipLaunchKernelGGL((dpcl_gram_u_kernel<2>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
         case 3: {
             const bool al = (((uintptr_t)U & 15) == 0);
-            if (E == 40 && S == 2 && al && dpcl_gram_f16()) hipLaunchKernelGGL((dpcl_gram_u16_kernel<40, 2>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, nchunk, fin);
-            else if (E == 40 && S == 3 && al && dpcl_gram_f16()) hipLaunchKernelGGL((dpcl_gram_u16_kernel<40, 3>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, nchunk, fin);
-            else if (E == 40 && S == 2 && al) hipLaunchKernelGGL((dpcl_gram_u_kernel<3, 40, 2>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin);
-            else if (E == 40 && S == 3 && al) hipLaunchKernelGGL((dpcl_gram_u_kernel<3, 40, 3>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin);
-            else hipLaunchKernelGGL((dpcl_gram_u_kernel<3, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin);
+            if (E == 40 && S == 2 && al) hipLaunchKernelGGL((dpcl_gram_u16_kernel<40, 2>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, nchunk, fin);
+            else if (E == 40 && S == 3 && al) hipLaunchKernelGGL((dpcl_gram_u16_kernel<40, 3>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, nchunk, fin);
+            else hipLaunchKernelGGL((dpcl_gram_u_kernel<3>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin);
             break;
         }
-        default: hipLaunchKernelGGL((dpcl_gram_u_kernel<4, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
+        default: hipLaunchKernelGGL((dpcl_gram_u_kernel<4>), grid, dim3(256), 0, st, U, Y, cntp, inv, V_out, part, TF, E, S, nchunk, fin); break;
     }
     return ams_check_launch();
 }
@@ -1383,19 +1365,17 @@ ams_status ams_dpcl_loss_bwd_u(const float* U, const float* Y, const float* inv,
     if (E + S > 64) return AMS_E_INVALID_ARG;
     dim3 grid(ceil_div(TF, BCHUNK), B);
     switch (NT) {
-        case 1: hipLaunchKernelGGL((dpcl_bwd_u_kernel<1, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
-        case 2: hipLaunchKernelGGL((dpcl_bwd_u_kernel<2, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
+        case 1: hipLaunchKernelGGL((dpcl_bwd_u_kernel<1>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
+        case 2: hipLaunchKernelGGL((dpcl_bwd_u_kernel<2>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
         case 3: {
             const bool al = (((uintptr_t)U & 15) == 0) && (((uintptr_t)dU & 15) == 0);
             const dim3 grid2(ceil_div(TF, BCH2), B);
-            if (E == 40 && S == 2 && al && dpcl_direct()) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 2>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
-            else if (E == 40 && S == 3 && al && dpcl_direct()) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 3>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
-            else if (E == 40 && S == 2 && al) hipLaunchKernelGGL((dpcl_bwd_u_kernel<3, 40, 2>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out);
-            else if (E == 40 && S == 3 && al) hipLaunchKernelGGL((dpcl_bwd_u_kernel<3, 40, 3>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out);
-            else hipLaunchKernelGGL((dpcl_bwd_u_kernel<3, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out);
+            if (E == 40 && S == 2 && al) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 2>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
+            else if (E == 40 && S == 3 && al) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 3>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
+            else hipLaunchKernelGGL((dpcl_bwd_u_kernel<3>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out);
             break;
         }
-        default: hipLaunchKernelGGL((dpcl_bwd_u_kernel<4, 0, 0>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
+        default: hipLaunchKernelGGL((dpcl_bwd_u_kernel<4>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
     }
     return ams_check_launch();
 }

@@ -38,21 +38,16 @@ constexpr size_t AMS_SK_SLOT_BYTES = (128 * 256 + 256) * sizeof(float);     // t
 std::atomic<int> g_gemm_arith{-1};        // -1: not chosen yet (AMS_GEMM_X6, default 1), 0: native f32 MFMA, 1: bf16x6
 
 // Tuning overrides (A/B runs only): read from the environment ONCE per process, never on the launch path.
-struct GemmTuning { int group_m, splits, x6cfg, x6rule, x6persist, sk; bool noprio, novec, f16x3; double x6waste; bool c_vec; };
+struct GemmTuning { int group_m, splits, x6cfg, sk; bool novec, f16x3; };
 inline const GemmTuning& tuning() {
     static const GemmTuning t = [] {
-        GemmTuning v{0, 0, -1, 2, 1, 1, false, false, true, 1.30, true};
-        if (const char* f = getenv("AMS_GEMM_CVEC")) v.c_vec = atoi(f) != 0;    // 0: the x6 epilogue stores columns as the MFMA leaves them (dword stores)
+        GemmTuning v{0, 0, -1, 1, false, true};
         if (const char* f = getenv("AMS_GEMM_SK")) v.sk = atoi(f);        // stream-K: 0 off, 1 the tail of multi-round launches where the cost model prefers it (default), 2 wherever it applies
-        if (const char* f = getenv("AMS_GEMM_X6WASTE")) v.x6waste = atof(f);
         if (const char* f = getenv("AMS_GEMM_GROUP_M")) v.group_m = atoi(f);
         if (const char* f = getenv("AMS_GEMM_SPLITS")) v.splits = atoi(f);
-        v.noprio = getenv("AMS_GEMM_NOPRIO") != nullptr;
-        { const char* e = getenv("AMS_X6_PERSIST"); v.x6persist = e ? atoi(e) : 1; }
         { const char* e = getenv("AMS_GEMM_F16X3"); v.f16x3 = !(e && atoi(e) == 0); }
         v.novec = getenv("AMS_GEMM_NOVEC") != nullptr;
-        if (const char* f = getenv("AMS_GEMM_X6CFG")) v.x6cfg = atoi(f);       // force one bf16x6 tile configuration (0, 1 or 3: X6Cfg)
-        if (const char* f = getenv("AMS_GEMM_X6RULE")) v.x6rule = atoi(f);
+        if (const char* f = getenv("AMS_GEMM_X6CFG")) { const int c = atoi(f); if (c == 0 || c == 3) v.x6cfg = c; }     // force one bf16x6 tile configuration (X6Cfg)
         return v;
     }();
     return t;
@@ -60,9 +55,6 @@ inline const GemmTuning& tuning() {
 
 #ifndef AMS_GEMM_BK
 #define AMS_GEMM_BK 8
-#endif
-#ifndef AMS_GEMM_XCD_FLAT
-#define AMS_GEMM_XCD_FLAT 1
 #endif
 // Arithmetic of the 16-byte-fetch products: 1 = bf16x6 (exact 3-way bf16 split of both f32 operands, six bf16 MFMA products, f32
 // accumulation: f32-level error at 2.7x the f32 MFMA ceiling), 0 = native v_mfma_f32_32x32x2_f32.  Process-wide; the default comes
@@ -87,9 +79,6 @@ constexpr int X6_BK = 32;           // k-tile of the bf16x6 kernel
 #endif
 #ifndef AMS_GEMM_X6_US16_2
 #define AMS_GEMM_X6_US16_2 1.35
-#endif
-#ifndef AMS_GEMM_X6_US16_1
-#define AMS_GEMM_X6_US16_1 2.35
 #endif
 constexpr int PAD_T = 2;   // k-contiguous source, transposed scalar LDS writes: stride 130 -> conflict-free
 constexpr int PAD_V = 4;   // m/n-contiguous source, float4 LDS writes: stride 132 keeps 16B alignment
@@ -198,21 +187,12 @@ __device__ __forceinline__ void locate_tile(GemmArgs& g, int& split, int& tile_m
         const int nz = g.nbatch > 1 ? g.nbatch : 1;
         const int items = ntiles * g.splits * nz;               // == gridDim.x
         int item = vbid >= 0 ? vbid : (int)blockIdx.x;
-#if AMS_GEMM_XCD_FLAT
         const int q = items / 8, r = items % 8, xcd = item % 8, idx = item / 8;
         item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
         zb = item / (ntiles * g.splits);
         item -= zb * (ntiles * g.splits);
         split = item / ntiles;
         bid = item - split * ntiles;
-#else
-        zb = item / (ntiles * g.splits);                       // round-1 order: per-(z, split) plane, tiles dealt by x % 8
-        item -= zb * (ntiles * g.splits);
-        split = item / ntiles;
-        bid = item - split * ntiles;
-        const int q = ntiles / 8, r = ntiles % 8, xcd = bid % 8, idx = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-#endif
     }
     if (g.nbatch > 1) {                             // batched launch: same shape, shifted operands
         const long z = zb;
@@ -680,9 +660,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
-#ifndef AMS_SK_CAPPED
-#define AMS_SK_CAPPED 0
-#endif
 #ifndef AMS_X6_DBG
 #define AMS_X6_DBG 0        // timing anatomy only (WRONG results): 1 no split arithmetic, 2 no LDS writes, 4 no MFMAs, 8 no LDS reads, 16 no fetch in the loop
 #endif
@@ -690,12 +667,11 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 // Tile configurations: block BMX x BNX, WMC x WNC waves of (TM x 32) x (TN x 32).
 template <int CFG> struct X6Cfg;
 template <> struct X6Cfg<0> { static constexpr int BMX = 128, BNX = 128, WMC = 2, WNC = 2, TM = 2, TN = 2; };   // 4 waves, 48.75 KB
-template <> struct X6Cfg<1> { static constexpr int BMX = 256, BNX = 256, WMC = 2, WNC = 4, TM = 4, TN = 2; };   // 8 waves, 96.75 KB
 template <> struct X6Cfg<3> { static constexpr int BMX = 128, BNX = 256, WMC = 2, WNC = 4, TM = 2, TN = 2; };   // 8 waves, 72.75 KB
 constexpr int x6_plane(int rows) { return rows * 16 + 32; }     // bytes; +32: the four planes start 8 banks apart (16-byte row writes of one wave hit all four)
 constexpr int x6_oper(int rows) { return 3 * 4 * x6_plane(rows); }
-constexpr int x6_bm(int cfg) { return cfg == 1 ? 256 : 128; }
-constexpr int x6_bn(int cfg) { return (cfg == 1 || cfg == 3) ? 256 : 128; }
+constexpr int x6_bm(int) { return 128; }
+constexpr int x6_bn(int cfg) { return cfg == 3 ? 256 : 128; }
 constexpr int x6_lds(int cfg) { return x6_oper(x6_bm(cfg)) + x6_oper(x6_bn(cfg)); }
 
 __device__ __forceinline__ unsigned pk_bf16(float a, float b) {           // v_cvt_pk_bf16_f32: a -> bits 0..15, b -> bits 16..31
@@ -809,10 +785,9 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
     // PARTIAL: accumulators to the workgroup's slot as write-through stores, then a flag.  A workgroup runs its partial segment
     // FIRST and never waits before it has published, and an owner only waits for workgroups with a lower index on its own XCD.
     enum { W_FULL = 0, W_PART = 1, W_OWNER = 2 };
-    // The capped single-accumulator variants take ONE item and no stream-K share unless built with -DAMS_SK_CAPPED=1: the walk and the
-    // hand-off cost them ~40 VGPRs, and above 168 they no longer share a CU with a recurrence ring.
-    constexpr bool WALK = PERSIST || (AMS_SK_CAPPED && EPI == EPI_STORE);
-    const bool sk = WALK && g0.sk_rounds >= 0;
+    // The capped single-accumulator variants take ONE item and no stream-K share: the walk and the hand-off cost them ~40 VGPRs, and
+    // above 168 they no longer share a CU with a recurrence ring (forcing them under 168 spilled and measured slower).
+    const bool sk = PERSIST && g0.sk_rounds >= 0;
     const int nk_full = (g0.K + BK - 1) / BK;
     const int G = (int)gridDim.x;
     const int sk_x = (int)blockIdx.x & 7, sk_w = (int)blockIdx.x >> 3, sk_Gx = G >> 3;
@@ -1162,8 +1137,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] += accs[i][j];
         }
-        const bool more = WALK && wi + 1 < n_work;
-        const int cur_role = WALK ? role : W_FULL;
+        const bool more = PERSIST && wi + 1 < n_work;
+        const int cur_role = PERSIST ? role : W_FULL;
         // stream-K slots: the accumulators in FRAGMENT order (lane l's float4 q of MFMA tile (i, j) of wave w at
         // ((w TM TN + i TN + j) 4 + q) KB + 16 l: 64 lanes move 1 KB contiguous), then BNX column sums
         constexpr unsigned TILE_B = (unsigned)BMX * BNX * 4u;
@@ -1380,7 +1355,7 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
 }
 
 template <int AMODE, int BMODE, int CFG, int EPI = EPI_STORE, bool SEP = false, bool F16 = false>
-__global__ __launch_bounds__(X6Cfg<CFG>::WMC * X6Cfg<CFG>::WNC * 64, CFG == 0 ? 2 : ((AMS_SK_CAPPED && !SEP && EPI == EPI_STORE) ? 3 : 1)) void gemm_x6_kernel(const GemmArgs g) {
+__global__ __launch_bounds__(X6Cfg<CFG>::WMC * X6Cfg<CFG>::WNC * 64, CFG == 0 ? 2 : 1) void gemm_x6_kernel(const GemmArgs g) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[x6_lds(CFG)];
     x6_body<AMODE, BMODE, CFG, EPI, SEP, F16>(g, smem);
 }
@@ -1446,26 +1421,19 @@ __global__ void bsum_finish_kernel(const float* __restrict__ part, float* __rest
 // barrier stalls are not covered by a neighbour's MFMAs; the last term is the fp32 partial-slab round trip.
 struct TilePlan { int bm, bn, bk; double us16; bool alone; };   // block tile, the cost of 16 k of it for one workgroup (microseconds), one workgroup per CU by construction
 inline TilePlan f32_plan() { return {BM, BN, BK, 1.024, false}; }
-// bf16x6 tile configuration (X6Cfg) of an M x N output.  Default (rule 2): 128 x 256 (8 waves of 64 x 64) where it wastes under
-// 30 % of the columns it covers (AMS_GEMM_X6WASTE = 1.30; 1.10 until the fp16x3 products: with half the MFMAs per k-tile the
-// 8-wave tile wins even at N = 600 -> 768 -- LSTM dX 98 -> 87 us, dense dX 289 -> 277 us alone, the B = 64 step 3.14 -> 3.09 ms,
-// tools/probes/cfg_sweep.sh + tools/probes/ab_bench.sh), 128 x 128 otherwise -- both carry the second accumulator set (SEP) when they are not
-// residency-capped.  Rule 1 (AMS_GEMM_X6RULE=1) adds the 256 x 256 tile (8 waves of 128 x 64) where both sides fit: +0.7 % on the
-// step (projections 107 vs 121 us), but no registers for SEP -- its outputs carry the bf16 MFMA's truncation bias (-0.3 .. -1 ulp
-// each, coherent: the LSTM bias gradients, sums over 5120 rows downstream of it, were 1.2e-5 off the oracle instead of < 1e-6), so
-// it is not the default.  A residency-capped launch never takes it (8 waves x 256 VGPRs leave no room for a ring workgroup).
-// Rule 0: {256 x 256, 128 x 128} only.  (256 x 128 was measured too -- profiles/r02_i_gemm_x6_tile_configs.txt -- and lost to
-// 128 x 128 on every shape it suits.)
-inline int x6_choose_cfg(int M, int N, bool capped) {
-    if (tuning().x6cfg == 0 || tuning().x6cfg == 1 || tuning().x6cfg == 3) return tuning().x6cfg;
-    const bool m256 = (double)ceil_div(M, 256) * 256 <= 1.10 * M, n256 = (double)ceil_div(N, 256) * 256 <= tuning().x6waste * N;
-    const int rule = tuning().x6rule;
-    if (m256 && n256 && !capped && rule <= 1) return 1;
-    if (n256 && rule >= 1) return 3;
-    return 0;
+// bf16x6 tile configuration (X6Cfg) of an M x N output: 128 x 256 (8 waves of 64 x 64) where it wastes under 30 % of the columns it
+// covers (1.10 until the fp16x3 products: with half the MFMAs per k-tile the 8-wave tile wins even at N = 600 -> 768 -- LSTM dX
+// 98 -> 87 us, dense dX 289 -> 277 us alone, the B = 64 step 3.14 -> 3.09 ms, tools/probes/cfg_sweep.sh + tools/probes/ab_bench.sh),
+// 128 x 128 otherwise -- both carry the second accumulator set (SEP) when they are not residency-capped.
+// A 256 x 256 tile (8 waves of 128 x 64) was +0.7 % on the step but had no registers for SEP, so its outputs carried the bf16 MFMA's
+// truncation bias (LSTM bias gradients 1.2e-5 off the oracle instead of < 1e-6): retired.  256 x 128 lost to 128 x 128 everywhere.
+constexpr double X6_WASTE = 1.30;
+inline int x6_choose_cfg(int M, int N) {
+    if (tuning().x6cfg >= 0) return tuning().x6cfg;
+    return (double)ceil_div(N, 256) * 256 <= X6_WASTE * N ? 3 : 0;
 }
 inline TilePlan x6_plan(int cfg) {
-    return {x6_bm(cfg), x6_bn(cfg), X6_BK, cfg == 1 ? AMS_GEMM_X6_US16_1 : cfg == 0 ? AMS_GEMM_X6_US16 : AMS_GEMM_X6_US16_2, cfg != 0 && AMS_X6_OCC1};
+    return {x6_bm(cfg), x6_bn(cfg), X6_BK, cfg == 0 ? AMS_GEMM_X6_US16 : AMS_GEMM_X6_US16_2, cfg != 0 && AMS_X6_OCC1};
 }
 inline int choose_splits(int M, int N, int K, int nbatch, const TilePlan& tp, double* t_out = nullptr, int smax = 32) {
     const int tiles = ceil_div(M, tp.bm) * ceil_div(N, tp.bn) * nbatch;
@@ -1487,8 +1455,8 @@ inline int choose_splits(int M, int N, int K, int nbatch, const TilePlan& tp, do
 }
 // what a workspace query assumes: the process-wide arithmetic (a launch whose operands are not 16-byte addressable falls back to
 // the f32 kernel and re-plans within the workspace it is given)
-inline int choose_splits(int M, int N, int K, int nbatch, bool capped) {
-    return choose_splits(M, N, K, nbatch, use_x6() ? x6_plan(x6_choose_cfg(M, N, capped)) : f32_plan());
+inline int choose_splits(int M, int N, int K, int nbatch) {
+    return choose_splits(M, N, K, nbatch, use_x6() ? x6_plan(x6_choose_cfg(M, N)) : f32_plan());
 }
 inline size_t slab_bytes(int M, int N, int nbatch, int splits) { return splits <= 1 ? 0 : (size_t)nbatch * splits * M * N * sizeof(float); }
 
@@ -1521,6 +1489,9 @@ inline int device_cus() {
     if (!cus) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); if (cus <= 0) cus = 256; }
     return cus;
 }
+// persistent grid of the uncapped two-accumulator variants (x6_body): one resident set of workgroups -- the CUs rounded up to whole
+// XCDs x (2 for the 4-wave configuration, 1 for the 8-wave one) -- walks the items
+inline long x6_persist_cap(int cfg) { return (long)((device_cus() + 7) / 8 * 8) * (cfg == 0 ? 2 : 1); }
 
 // Stream-K plan of an x6 launch (x6_body): the resident grid G (a multiple of 8), the whole-tile rounds every workgroup runs, and the
 // model's time for it in the units of choose_splits (microseconds at the bf16x6 calibration).  rounds < 0: does not apply.
@@ -1556,14 +1527,14 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
                       AKc ? (g.K % 4 == 0 && g.K >= 4) : (g.M % 4 == 0 && g.M >= 4)) &&
                      (BKcc ? (g.K % 4 == 0 && g.K >= 4) : (g.N % 4 == 0 && g.N >= 4));
     const bool x6 = vec && use_x6();
-    const int cfg = x6 ? ((opt.force_cfg == 0 || opt.force_cfg == 3) && tuning().x6cfg < 0 ? opt.force_cfg : x6_choose_cfg(g.M, g.N, capped)) : 0;
+    const int cfg = x6 ? ((opt.force_cfg == 0 || opt.force_cfg == 3) && tuning().x6cfg < 0 ? opt.force_cfg : x6_choose_cfg(g.M, g.N)) : 0;
     // fp16x3 when the caller supplied bounds for both operands
-    const bool f16 = x6 && cfg != 1 && opt.amax_a && opt.amax_b && tuning().f16x3;
+    const bool f16 = x6 && opt.amax_a && opt.amax_b && tuning().f16x3;
     g.amax_a = f16 ? opt.amax_a : nullptr;
     g.amax_b = f16 ? opt.amax_b : nullptr;
     g.amax_out = x6 ? opt.amax_out : nullptr;
     g.c_vec = (g.N % 4 == 0) && (g.ldc % 4 == 0) && (g.c_zs % 4 == 0) && (g.bias_zs % 4 == 0) &&
-              (((uintptr_t)g.C | (uintptr_t)ws | (uintptr_t)g.bias) & 15) == 0 && tuning().c_vec;
+              (((uintptr_t)g.C | (uintptr_t)ws | (uintptr_t)g.bias) & 15) == 0;
     if (opt.amax_out && !x6) return AMS_E_INVALID_ARG;                    // only the x6 epilogue measures its output
     const TilePlan tp = x6 ? x6_plan(cfg) : f32_plan();
     const int tiles = ceil_div(g.M, tp.bm) * ceil_div(g.N, tp.bn);
@@ -1582,7 +1553,7 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     // stream-K instead of whole-tile rounds / split-K slabs (x6_body), where the caller lent scratch and the model prefers it
     SkPlan sk;
     g.sk_rounds = -1; g.sk_flags = nullptr; g.sk_slots = nullptr; g.sk_slot_floats = 0; g.amax_fold = 0;
-    if (x6 && cfg != 1 && (!capped || AMS_SK_CAPPED) && opt.sk_scratch && tuning().sk != 0 && tuning().splits <= 0 && AMS_GEMM_XCD_FLAT) {
+    if (x6 && !capped && opt.sk_scratch && tuning().sk != 0 && tuning().splits <= 0) {
         sk = sk_plan(tiles * nbatch, g.K, tp, wgcu);
         const size_t slot = (size_t)(tp.bm * tp.bn + tp.bn) * sizeof(float);
         if (sk.rounds >= 0 && (opt.sk_bytes < AMS_SK_FLAG_BYTES + (size_t)sk.grid * slot || (((uintptr_t)opt.sk_scratch) & 15))) sk.rounds = -1;
@@ -1614,13 +1585,12 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     g.bsum_accumulate = bsum_accumulate;
     g.nbatch = nbatch;
     dim3 grid((unsigned)((long)tiles * splits * nbatch));
-    const bool prio_off = tuning().noprio;
-    g.hiprio = (!capped && !prio_off) ? 1 : 0;
+    g.hiprio = !capped;
     if (g.amax_out) {
         // the launch folds its output maximum itself when the caller lent scratch (words [512, 1025) of its flag area) and the grid fits
         unsigned gx = grid.x;
         if (sk.rounds >= 0) gx = sk.grid;
-        else if (x6 && tuning().x6persist > 0 && !capped && cfg != 1) { const long cap = (long)((device_cus() + 7) / 8 * 8) * (cfg == 0 ? 2 : 1) * tuning().x6persist; if ((long)gx > cap) gx = (unsigned)cap; }
+        else if (!capped && (long)gx > x6_persist_cap(cfg)) gx = (unsigned)x6_persist_cap(cfg);
         if (opt.sk_scratch && opt.sk_bytes >= AMS_SK_FLAG_BYTES && gx <= 512 && (((uintptr_t)opt.sk_scratch) & 15) == 0) {
             g.amax_fold = 1;
             g.sk_flags = (int*)opt.sk_scratch;
@@ -1630,13 +1600,8 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     // the side stream): unused dynamic LDS limits how many of these workgroups a CU admits, leaving registers/slots
     // for the recurrence.  An explicit argument of the entry points (LaunchOpt::lds_pad).
     if (x6) {
-        // persistent grid (x6_body, uncapped two-accumulator variants): one resident set of workgroups -- 256 CUs x (2 for the 4-wave configuration, 1 for the 8-wave
-        // ones) x AMS_X6_PERSIST (default 1; 0 = one workgroup per item as before) -- walks the items.
         if (sk.rounds >= 0) grid.x = sk.grid;
-        else if (tuning().x6persist > 0 && !capped && cfg != 1) {      // the variants launched with SEP = true below
-            const long cap = (long)((device_cus() + 7) / 8 * 8) * (cfg == 0 ? 2 : 1) * tuning().x6persist;
-            if ((long)grid.x > cap) grid.x = (unsigned)cap;
-        }
+        else if (!capped && (long)grid.x > x6_persist_cap(cfg)) grid.x = (unsigned)x6_persist_cap(cfg);      // the variants launched with SEP = true below
         // residency: the 128 x 128 configuration holds 48.75 KB of LDS (3 workgroups per CU by LDS, 2 by registers); a pad asks for
         // what it asks of the 16.8 KB f32 kernel (workgroups per CU), restated.  The 8-wave configurations are alone on a CU anyway.
         if (cfg == 0) {
@@ -1656,8 +1621,7 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
                 else hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 0, EPI_STORE, true, true>), grid, dim3(256), 0, st, g);
             } else if (capped) hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 0>), grid, dim3(256), (size_t)pad, st, g);
             else hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 0, EPI_STORE, true>), grid, dim3(256), 0, st, g);
-        } else if (cfg == 1) hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 1>), grid, dim3(512), 0, st, g);
-        else if (f16) {
+        } else if (f16) {
             if (capped) hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 3, EPI_STORE, false, true>), grid, dim3(512), 0, st, g);
             else hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 3, EPI_STORE, true, true>), grid, dim3(512), 0, st, g);
         } else if (capped) hipLaunchKernelGGL((gemm_x6_kernel<AMODE, BMODE, 3>), grid, dim3(512), 0, st, g);
@@ -1774,7 +1738,7 @@ size_t ams_gemm_sk_scratch_bytes(void) {
 
 size_t ams_gemm_workspace_bytes(int M, int N, int K, int nbatch, int lds_pad) {
     if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return 0;
-    int splits = choose_splits(M, N, K, nbatch, lds_pad > 0);
+    int splits = choose_splits(M, N, K, nbatch);
     if (tuning().splits > 0) splits = tuning().splits;
     return slab_bytes(M, N, nbatch, splits);
 }
@@ -2017,44 +1981,12 @@ __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict
     }
 }
 
-// df[k,n] = sum_{r,t} xpad[r, pos[r/rdiv,t,n] + k - pl] * v[r,t,n].  Block = 256 consecutive taps k of one filter n and one
-// slice of rows (grid.z): pos / v are uniform per iteration (scalar loads), x is a coalesced 1 KB read.
-__global__ __launch_bounds__(256) void gather_filter_grad_kernel(const float* __restrict__ x, const float* __restrict__ v,
-                                                                 const int32_t* __restrict__ pos, float* __restrict__ part, int R,
-                                                                 int L, int W, int N, int T, int pl, int rdiv, int rows_per_z) {
-    const int n = blockIdx.y;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    const int r_lo = blockIdx.z * rows_per_z, r_hi = min(R, r_lo + rows_per_z);
-    float s = 0.f;
-    for (int r = r_lo; r < r_hi; ++r) {
-        const float* xr = x + (long)r * L;
-        const int32_t* pr = pos + ((long)(r / rdiv) * T) * N + n;
-        const float* vr = v + ((long)r * T) * N + n;
-        // eight (position, value) pairs and their eight window samples in flight per round: the loop was one dependent chain of
-        // scalar load -> vector load -> FMA per iteration (~1.5 us each, 3.1 ms per launch at the path-B shape); same summation order
-        for (int t = 0; t < T; t += 8) {
-            int p[8];
-            float val[8], xv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int tt = min(t + u, T - 1);
-                p[u] = pr[(long)tt * N] + k - pl;
-                val[u] = vr[(long)tt * N];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) xv[u] = xr[min(max(p[u], 0), L - 1)];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (t + u < T && p[u] >= 0 && p[u] < L) s += xv[u] * val[u];
-        }
-    }
-    if (k < W) part[((long)blockIdx.z * W + k) * N + n] = s;
-}
-// LDS-staged form of the same sum (the default).  For one (row r, frame t) the windows of ALL filters start inside one pooling
-// window, so they lie inside one short segment of the row: [min_n pos, max_n pos + W).  The kernel above re-reads that segment
-// from L2 once per filter (4 KB x R*T*N = 16 GB per launch at the path-B shape, 2.2 ms); here a workgroup = 256 taps x 64 filters
-// x a slice of the (r, t) pairs stages the part of the segment its taps need ONCE in LDS and every thread accumulates 4 taps x 16
-// filters in registers from it (8-byte LDS reads; a second copy of the segment shifted by one sample serves the odd shifts).
+// df[k,n] = sum_{r,t} xpad[r, pos[r/rdiv,t,n] + k - pl] * v[r,t,n].  For one (row r, frame t) the windows of ALL filters start inside
+// one pooling window, so they lie inside one short segment of the row: [min_n pos, max_n pos + W).  A form with one workgroup per
+// filter re-read that segment from L2 once per filter (4 KB x R*T*N = 16 GB per launch at the path-B shape, 2.2 ms); here a
+// workgroup = 256 taps x 64 filters x a slice of the (r, t) pairs stages the part of the segment its taps need ONCE in LDS and
+// every thread accumulates 4 taps x 16 filters in registers from it (8-byte LDS reads; a second copy of the segment shifted by one
+// sample serves the odd shifts).
 constexpr int GF_TAPS = 256, GF_FILT = 64, GF_SEG = 1536;      // segment capacity: spread of the positions + 256 taps + 1
 constexpr int GF_QB = 4;                                        // (row, frame) pairs per round: wave w prepares pair w, ONE barrier triple
                                                                 // per four pairs (round 5: one pair per round was three barriers around 64
@@ -2355,9 +2287,8 @@ ams_status ams_front_maxpool_fwd(const float* x, const float* f, float* y, long 
                 if (mp_aa && mp_ab && tuning().f16x3) {
                     g.amax_a = mp_aa; g.amax_b = mp_ab;
                     // N a multiple of 256: the 128 x 256 tile (8 waves) -- every frame sample is split and staged once per 256 filters
-                    // instead of once per 128, and that stage, not the MFMAs, is what this kernel spends its time on (AMS_MAXPOOL_CFG=0: 128 x 128)
-                    static const bool wide = [] { const char* e = getenv("AMS_MAXPOOL_CFG"); return !(e && e[0] == '0'); }();
-                    if (wide && N % 256 == 0)
+                    // instead of once per 128, and that stage, not the MFMAs, is what this kernel spends its time on
+                    if (N % 256 == 0)
                         hipLaunchKernelGGL((gemm_x6_kernel<A_FRAMES, B_ROW, 3, EPI_MAXPOOL, true, true>), dim3(tiles_m * (N / 256), 1), dim3(512), 0, st, g);
                     else
                     hipLaunchKernelGGL((gemm_x6_kernel<A_FRAMES, B_ROW, 0, EPI_MAXPOOL, true, true>), grid, dim3(256), 0, st, g);
@@ -2392,9 +2323,8 @@ ams_status ams_transpose_f32(const float* in, float* out, int rows, int cols, vo
     return ams_check_launch();
 }
 
-static int gather_nz(int R) { int nz = R / 16; if (nz < 1) nz = 1; if (nz > 16) nz = 16; return nz; }
-// slices of the (r, t) pairs of the LDS-staged form: ~1024 workgroups in all
-static int gather_nz_lds(int R, int W, int N, int T) {
+// slices of the (r, t) pairs: ~1024 workgroups in all
+static int gather_nz(int R, int W, int N, int T) {
     const long tiles = (long)ceil_div(W, GF_TAPS) * ceil_div(N, GF_FILT);
     long nz = 1024 / tiles;
     if (nz < 1) nz = 1;
@@ -2402,11 +2332,8 @@ static int gather_nz_lds(int R, int W, int N, int T) {
     if (nz > (long)R * T) nz = (long)R * T;
     return (int)nz;
 }
-static bool gather_use_lds() { static const bool v = getenv("AMS_GATHER_LDS") == nullptr || atoi(getenv("AMS_GATHER_LDS")) != 0; return v; }
 size_t ams_gather_filter_grad_workspace_bytes(int R, int W, int N) {
-    // the caller does not pass T: size for the larger of the two forms (<= 128 slices)
-    const size_t a = (size_t)gather_nz(R) * W * N * sizeof(float), b = (size_t)128 * W * N * sizeof(float);
-    return gather_use_lds() ? (a > b ? a : b) : a;
+    return (size_t)128 * W * N * sizeof(float);          // the caller does not pass T: the most slices gather_nz() gives
 }
 
 // df[k,n] = sum_{r,t} xpad[r, pos[r/rdiv,t,n] + k - pl] * v[r,t,n]   (max-pool front: x = waveforms, v = dy, rdiv = 1;
@@ -2416,17 +2343,10 @@ ams_status ams_gather_filter_grad(const float* x, const float* v, const int32_t*
     AMS_REQUIRE(x && v && pos && df && ws && R > 0 && L > 0 && W > 0 && N > 0 && T > 0 && rdiv > 0);
     if (ws_bytes < ams_gather_filter_grad_workspace_bytes(R, W, N)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
-    if (gather_use_lds()) {
-        const int nz = gather_nz_lds(R, W, N, T);
-        const long ppz = ((long)R * T + nz - 1) / nz;
-        hipLaunchKernelGGL(gather_filter_grad_lds_kernel, dim3(ceil_div(W, GF_TAPS), ceil_div(N, GF_FILT), nz), dim3(256), 0, st, x, v, pos,
-                           (float*)ws, R, L, W, N, T, (W - 1) / 2, rdiv, ppz);
-        hipLaunchKernelGGL(gather_filter_reduce_kernel, dim3(ceil_div((long)W * N, 256)), dim3(256), 0, st, (const float*)ws, df, (long)W * N, nz);
-        return ams_check_launch();
-    }
-    const int nz = gather_nz(R), rpz = ceil_div(R, nz);
-    hipLaunchKernelGGL(gather_filter_grad_kernel, dim3(ceil_div(W, 256), N, nz), dim3(256), 0, st, x, v, pos, (float*)ws, R, L, W, N, T,
-                       (W - 1) / 2, rdiv, rpz);
+    const int nz = gather_nz(R, W, N, T);
+    const long ppz = ((long)R * T + nz - 1) / nz;
+    hipLaunchKernelGGL(gather_filter_grad_lds_kernel, dim3(ceil_div(W, GF_TAPS), ceil_div(N, GF_FILT), nz), dim3(256), 0, st, x, v, pos,
+                       (float*)ws, R, L, W, N, T, (W - 1) / 2, rdiv, ppz);
     hipLaunchKernelGGL(gather_filter_reduce_kernel, dim3(ceil_div((long)W * N, 256)), dim3(256), 0, st, (const float*)ws, df, (long)W * N, nz);
     return ams_check_launch();
 }

@@ -19,17 +19,13 @@
  * variable is read ONCE per process (function-local static), never on the launch path, selects between code paths that the tests hold
  * to the same oracle, and exists for A/B measurements and fault-injection tests; a deployment sets none of them.
  *   products (csrc/gemm.hip)   AMS_GEMM_X6 (initial value of ams_gemm_set_arith: 0 = native f32 MFMA), AMS_GEMM_F16X3 (0 = ignore operand
- *                              bounds: bf16x6), AMS_GEMM_SK (stream-K 0/1/2), AMS_GEMM_CVEC (0 = dword epilogue stores), AMS_GEMM_X6CFG,
- *                              AMS_GEMM_X6RULE, AMS_GEMM_X6WASTE (tile choice), AMS_X6_PERSIST (0 = one tile per workgroup),
+ *                              bounds: bf16x6), AMS_GEMM_SK (stream-K 0/1/2), AMS_GEMM_X6CFG (force tile configuration 0 or 3),
  *                              AMS_GEMM_SPLITS, AMS_GEMM_GROUP_M (split-K / band height overrides), AMS_GEMM_NOVEC (force the dword-fetch
- *                              f32 kernel), AMS_GEMM_NOPRIO, AMS_MAXPOOL_CFG (0 = 128x128 tile for the fused conv + max-pool),
- *                              AMS_GATHER_LDS (0 = register form of ams_gather_filter_grad), AMS_MAXPOOL_PS (0 = path B's product cuts its operands
- *                              in the kernel also where the pre-split form applies)
+ *                              f32 kernel), AMS_MAXPOOL_PS (0 = path B's product cuts its operands in the kernel also where the pre-split
+ *                              form applies)
  *   recurrence (lstm*.hip)     AMS_LSTM_RING_X6, AMS_LSTM_RING_F16, AMS_LSTM_RING_BWD_F16 (arithmetic of the rings' recurrent products),
- *                              AMS_LSTM_RING_SAFE (write-through hand-off), AMS_LSTM_RING_CUS (pretend a smaller device: fallback tests),
- *                              AMS_LSTM_XCD, AMS_LSTM_FWD_PIPE (per-step fallback kernels: grid order, fetch pipelining)
- *   losses / k-means           AMS_DPCL_LDS (1 = LDS-staged DPCL passes), AMS_DPCL_GRAM_F16 (0 = the fused forward's Gram on the f32 MFMA),
- *                              AMS_KM_TRIES (0 = one workgroup per try), AMS_KM_SOFT (0 = soft accumulation inside kmeans_pass_kernel)
+ *                              AMS_LSTM_RING_SAFE (write-through hand-off), AMS_LSTM_RING_CUS (pretend a smaller device: fallback tests)
+ *   k-means                    AMS_KM_TRIES (0 = one workgroup per try), AMS_KM_SOFT (0 = soft accumulation inside kmeans_pass_kernel)
  */
 #ifndef AMS_H
 #define AMS_H
