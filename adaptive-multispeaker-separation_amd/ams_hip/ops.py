@@ -801,15 +801,21 @@ def backward_product(dU2, W2, amax, owner, out=None, label=''):
 
 def gemm_at_b_colsum(A, B, out, bsum, accumulate=True, amax=None, ldc=None):
     """out[M,N] (+)= A^T B and bsum[N] (+)= column sums of B in ONE pass over B (A [K,M], B [K,N] row-major).  Returns False when
-    the shapes / alignments do not allow the fused form (the caller then uses gemm + colsum)."""
+    the SHAPES do not allow the fused form (the caller then uses gemm + colsum).  The entry point also wants A, B and bsum 16-byte
+    aligned (include/ams.h): operands whose shapes fit but whose BASE does not (a slice of a flat buffer) are served here by the two
+    launches that take any base -- gemm and colsum, nothing is copied -- and the answer is True: out and bsum hold the results."""
     K, M = A.shape
     N = B.shape[1]
     ldc = out.stride(0) if ldc is None else ldc
     ok = (M % 4 == 0 and N % 4 == 0 and A.stride(0) % 4 == 0 and B.stride(0) % 4 == 0 and A.stride(1) == 1 and B.stride(1) == 1
-          and out.stride(-1) == 1 and bsum.stride(-1) == 1 and bsum.data_ptr() % 16 == 0
-          and all(t.data_ptr() % 16 == 0 for t in (A, B)) and not NOVEC)
+          and out.stride(-1) == 1 and bsum.stride(-1) == 1 and not NOVEC)
     if not ok:
         return False
+    if any(t.data_ptr() % 16 for t in (A, B, bsum)):
+        gemm(A, B, transA=True, out=out, accumulate=accumulate, M=M, N=N, K=K, lda=A.stride(0), ldb=B.stride(0), ldc=ldc, amax=amax,
+             key=('at_b_colsum', M, N, K))
+        colsum_into(B if B.is_contiguous() else B.contiguous(), bsum, accumulate)
+        return True
     lib = load()
     pad = LDS_PAD[0]
     nb = lib.ams_gemm_workspace_bytes(M, N, K, 1, pad)

@@ -161,7 +161,9 @@ ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, cons
 
 /* C[M,N] (+)= A^T . B with A stored [K, M] and B [K, N], AND bsum_out[N] (+)= column sums of B in the same pass over B: the
  * weight and bias gradients of Conv1D (utils/ops.py:501-503) and of a BLSTM layer's input kernels from one read of dY / dZ.  M, N, lda,
- * ldb multiples of 4, 16-byte aligned operands; bsum_ws = 32 * N floats of scratch (16-byte aligned). */
+ * ldb multiples of 4, 16-byte aligned operands; bsum_ws = 32 * N floats of scratch (16-byte aligned).  A, B or bsum_ws off a 16-byte
+ * boundary is AMS_E_INVALID_ARG, and so is such a bsum_out in a launch that takes the stream-K scratch; C may start anywhere (4-byte
+ * stores then).  Odd bases: ops.gemm_at_b_colsum runs ams_gemm_f32 + ams_colsum, which take any base, when only a base is off. */
 ams_status ams_gemm_f32_at_b_colsum(int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc,
                                     int accumulate, float* bsum_out, int bsum_accumulate, float* bsum_ws, const float* amax_a,
                                     const float* amax_b, int lds_pad, void* ws, size_t ws_bytes, void* sk_scratch, size_t sk_bytes,
