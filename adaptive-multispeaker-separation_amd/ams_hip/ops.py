@@ -1570,6 +1570,31 @@ def stage_inputs(src, dst, src2=None, dst2=None, want_amax=True):
     return am
 
 
+def mix_gather(pool, utt_off, plan, plan_keys, first, B, L):
+    """One batch of a record dataset from the device-resident pool (include/ams.h: ams_mix_gather; data/resident.py): pool fp32 [N],
+    utt_off int64 [U], plan int32 [n, S, 2] = (utterance, chunk), plan_keys int32 [n, S]; examples first .. first + B of the plan.
+    Returns mix [B, L], non_mix [B, S, L] -- views of ONE flat buffer [B L | B S L], so a captured step stages them with one launch
+    (models/network.py::_stage) -- and ind [B, S] int32.  One launch; the plan's entries are trusted (the planner validated them)."""
+    for t, dt in ((pool, torch.float32), (utt_off, torch.int64), (plan, torch.int32), (plan_keys, torch.int32)):
+        if not t.is_cuda:
+            raise AmsError('ams_hip ops need device tensors (there is no CPU fallback)')
+        if t.dtype != dt or not t.is_contiguous():
+            raise AmsError('mix_gather needs a contiguous %s tensor, got %s %s' % (dt, t.dtype, tuple(t.stride())))
+    first, B, L = int(first), int(B), int(L)
+    if plan.dim() != 3 or plan.shape[2] != 2 or tuple(plan_keys.shape) != tuple(plan.shape[:2]) or pool.dim() != 1 or utt_off.dim() != 1:
+        raise AmsError('mix_gather: plan [n, S, 2] / plan_keys [n, S] / pool [N] / utt_off [U] expected, got %s %s %s %s'
+                       % (tuple(plan.shape), tuple(plan_keys.shape), tuple(pool.shape), tuple(utt_off.shape)))
+    n, S = int(plan.shape[0]), int(plan.shape[1])
+    if B < 1 or L < 1 or first < 0 or first + B > n:
+        raise AmsError('mix_gather: examples %d .. %d of a plan of %d' % (first, first + B, n))
+    flat = torch.empty(B * L + B * S * L, dtype=torch.float32, device=pool.device)
+    mix, non_mix = flat[:B * L].view(B, L), flat[B * L:].view(B, S, L)
+    ind = torch.empty((B, S), dtype=torch.int32, device=pool.device)
+    check(load().ams_mix_gather(_p(pool), _p(utt_off), _p(plan), _p(plan_keys), first, _p(mix), _p(non_mix), _p(ind), B, S, L, _s()),
+          'ams_mix_gather')
+    return mix, non_mix, ind
+
+
 def clip_scale(ss, pre_scale, clip):
     """1-element device tensor clip / max(sqrt(ss) * pre_scale, clip) (tf.clip_by_global_norm, network.py:185-190): no host sync."""
     out = torch.empty(1, dtype=torch.float32, device=ss.device)

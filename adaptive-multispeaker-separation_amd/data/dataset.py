@@ -9,6 +9,7 @@ Two sources honour the same OUTPUT contract -- ``next_mix [B,L]``, ``next_non_mi
     -> zip S gender streams -> drop tuples with a repeated speaker -> sum -> batch), see ``RecordStream`` / ``MixtureStream``.
     tf.data's shuffle buffers draw from TF's own RNG, so the ORDER of examples differs from a TensorFlow run; the set of examples
     an epoch yields and every per-example value are the same.
+    ``TFDataset(resident=True)`` or ``AMS_DATA_RESIDENT=1`` serves the same batches from a device-resident pool (data/resident.py).
 """
 import numpy as np
 import torch
@@ -177,6 +178,7 @@ class TFDataset(object):
         self.pool_batches = int(kwargs.get('synthetic_pool') or 8)
         # real data: the reference's TFRecord files next to config.workdir (or AMS_DATA_DIR)
         self.records = None
+        self.resident = False                                           # record datasets only
         name = kwargs.get('dataset')
         if name and name != 'synthetic':
             import os
@@ -191,6 +193,12 @@ class TFDataset(object):
             self._lengths = {}
             self._epochs = {}
             self.hip_graph = bool(kwargs.get('hip_graph'))
+            # device-resident path (data/resident.py): the split's audio uploaded once, a pass planned as an index table, a batch = one
+            # gather launch.  Opt-in (keyword, or AMS_DATA_RESIDENT=1); the batches are those of the host path, call for call.
+            resident = kwargs.get('resident')
+            self.resident = bool(resident) if resident is not None else os.environ.get('AMS_DATA_RESIDENT', '0') == '1'
+            self._pools = {}                                            # split -> resident.ResidentRecords
+            self._plans = {}                                            # (split, L, drop_remainder) -> (epoch, resident.Plan)
 
         g = get_default_graph()
         with g.variable_scope('dataset'):
@@ -224,8 +232,25 @@ class TFDataset(object):
         world = self.dist.world_size if self.dist is not None else 1
         return world > 1 or (self.hip_graph and split == self.TRAIN)
 
+    def _plan(self, split, L, epoch):
+        """The index plan of one pass, uploaded once per (split, L, epoch); the pool of the split is loaded on first use."""
+        from data import resident
+        r = self.records
+        rec = self._pools.get(split)
+        if rec is None:
+            rec = self._pools[split] = resident.ResidentRecords(r['folder'], split, r['normalize'], self.device)
+        key = (split, L, self._drop_remainder(split))
+        have = self._plans.get(key)
+        if have is None or have[0] != epoch:
+            have = self._plans[key] = (epoch, resident.plan_pass(rec, r['sex'], self.S, L, self.batch_size, r['no_random_picking'],
+                                                                  epoch, key[2]).upload(rec.pool.device))
+        return rec, have[1]
+
     def _stream(self, split, L, epoch):
         r = self.records
+        if self.resident:
+            from data import resident
+            return resident.PlanBatches(self._plan(split, L, epoch)[1])
         return record_mixture_stream(r['folder'], split, r['sex'], self.S, L, self.batch_size, r['normalize'],
                                      r['no_random_picking'], epoch, self._drop_remainder(split))
 
@@ -252,6 +277,9 @@ class TFDataset(object):
             if k == rank:
                 out = b
         self.cursor[split] += 1
+        if self.resident:
+            from data import resident
+            return resident.gather(self._pools[split], *out)
         return tuple(torch.from_numpy(a).to(self.device) for a in out)
 
     def length(self, split):

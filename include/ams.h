@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define AMS_ABI_VERSION 9
+#define AMS_ABI_VERSION 10
 
 typedef int32_t ams_status;
 #define AMS_OK 0
@@ -438,6 +438,26 @@ ams_status ams_pair_combine_fwd(const float* stats, const float* D2, const int* 
 ams_status ams_pair_combine_bwd(const float* stats, const float* D2, const int* perms, const float* gout, const int* pbest,
                                 const int* jbest, float* gstats, float* gD2, int B, int S, int P, int mode, float cl, float cs,
                                 void* stream);
+
+/* ---- batch assembly from a device-resident sample pool (ABI 10; csrc/mix.hip)   data/dataset.py:462-491 of the reference ----
+ * The record datasets' chunk -> zip -> sum -> batch stages (data/dataset.py: RecordStream / MixtureStream / batched) as ONE launch over
+ * audio that was uploaded once (data/resident.py: ResidentRecords): what changes from batch to batch is an index table.
+ *   pool       every utterance of a split, float32, utterance u at pool[utt_off[u] ...); utt_off int64 -- the pool of a real corpus
+ *              exceeds 2^31 floats, offsets are 64-bit from the table to the address
+ *   plan       int32 [n, S, 2] = (utterance, chunk) of source s of example j, a whole pass; plan_keys int32 [n, S] the speaker keys
+ *   first      the pass-wide index of this batch's first example (batch k of size B: first = k * B)
+ * For b < B, j = first + b, (u, c) = plan[j, s]:   non_mix[b, s, :] = pool[utt_off[u] + c L ... + L),   ind[b, s] = plan_keys[j, s],
+ * mix[b, :] = ((r0 + r1) + r2) ... over the S rows in source order with plain f32 adds (no FMA, no wider accumulator): the bits of
+ * numpy's np.stack(rows).sum(axis = 0), so a batch equals the host pipeline's bit for bit.  mix [B, L], non_mix [B, S, L], ind [B, S].
+ * The kernel TRUSTS the plan: the caller guarantees first + B <= n, 0 <= u, and (c + 1) L <= the utterance's length (the planner
+ * validates this on the host).  Grid (ceil(L / 1024), B), one float4 of positions per thread, no LDS, no atomics, no workspace.
+ * L % 4 == 0 with pool, mix, non_mix 16-byte aligned: 16-byte stores, and 16-byte loads of every chunk that starts on a 16-byte
+ * boundary (all of them when every utt_off is a multiple of 4); anything else: dword accesses, any base.
+ * AMS_E_INVALID_ARG: S outside 1 .. 6, B, L < 1, B > 65535, L > 2^30, first < 0, a NULL pointer; nothing is launched then.
+ * Memory: the pool is the split's audio as float32 (LibriSpeech train-clean-100 at 8 kHz: ~11.5 GB), the two tables 12 bytes per
+ * source and example of a pass.  Bytes moved per batch: (2 S + 1) B L 4. */
+ams_status ams_mix_gather(const float* pool, const long long* utt_off, const int32_t* plan, const int32_t* plan_keys, long first,
+                          float* mix, float* non_mix, int32_t* ind, int B, int S, int L, void* stream);
 
 /* ---- K20 mask application   models/network.py:577-581 ---- */
 ams_status ams_apply_masks_fwd(const float* X, const float* masks, float* sep, int B, int S, long TF, void* stream);
