@@ -1,0 +1,100 @@
+# coding: utf-8
+"""python -m experiments.evaluation.separate --model_folder ... --sortofmodel {STFT,front}[_enhanced]_{DPCL,L41}
+       --input mix.wav --output_prefix out [--hop H]
+
+Separate one whole recording: the model's inference recipe (the same ones experiments/evaluation/eval.py uses) on overlapping chunks
+of --chunk_size samples, the chunk outputs tracked across the chunk borders and cross-faded on the GPU (Network.separate_recording,
+ams_hip/stitch.py).  Input: 16-bit PCM mono .wav at config.fs, or .npy float32 [N].  Output: <prefix>_<k>.wav (or .npy for an .npy
+input), k = 0 .. nb_speakers - 1.  There is no resampling and no channel mixing: anything else is refused."""
+import wave
+
+import numpy as np
+
+import config
+
+
+def build_parser():
+    from utils.trainer import MyArgs
+    p = MyArgs()
+    p.parser.add_argument('--model_folder', help='Path to the Model folder to load', required=True)
+    p.parser.add_argument('--sortofmodel', help='Sort of model', required=True)
+    p.parser.add_argument('--input', help='Recording to separate: 16-bit PCM mono .wav at %d Hz, or .npy float32 [N]' % config.fs,
+                          required=True)
+    p.parser.add_argument('--output_prefix', help='Outputs are written to <prefix>_<k>.wav (.npy for an .npy input)', required=True)
+    p.parser.add_argument('--hop', type=int, help='Samples between two chunks, ceil(chunk_size / 2) .. chunk_size - 1 '
+                          '(default: half a chunk)', required=False, default=None)
+    p.add_adapt_args()
+    p.add_separator_args()
+    return p
+
+
+def read_wav(path, fs=None):
+    """16-bit PCM mono at fs (default config.fs) -> float32 [N] in [-1, 1): samples / 32768."""
+    fs = config.fs if fs is None else fs
+    with wave.open(path, 'rb') as w:
+        if w.getnchannels() != 1:
+            raise SystemExit('%s has %d channels: one channel only (mix them down first)' % (path, w.getnchannels()))
+        if w.getsampwidth() != 2 or w.getcomptype() != 'NONE':
+            raise SystemExit('%s is not 16-bit PCM (%d bytes per sample, compression %s)' % (path, w.getsampwidth(), w.getcomptype()))
+        if w.getframerate() != fs:
+            raise SystemExit('%s has a sample rate of %d Hz: the models work at %d Hz and nothing here resamples'
+                             % (path, w.getframerate(), fs))
+        raw = w.readframes(w.getnframes())
+    return np.frombuffer(raw, dtype='<i2').astype(np.float32) / np.float32(32768.0)
+
+
+def write_wav(path, x, fs=None):
+    """float32 [N] -> 16-bit PCM mono: round(x * 32768) clipped symmetrically to +-32767.  Non-finite samples are refused."""
+    fs = config.fs if fs is None else fs
+    if not np.all(np.isfinite(x)):
+        raise SystemExit('%s: %d of %d samples are not finite; nothing written' % (path, int((~np.isfinite(x)).sum()), np.size(x)))
+    pcm = np.clip(np.rint(np.asarray(x, np.float64) * 32768.0), -32767, 32767).astype('<i2')
+    with wave.open(path, 'wb') as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(fs)
+        w.writeframes(pcm.tobytes())
+
+
+def read_input(path):
+    if path.endswith('.npy'):
+        x = np.load(path)
+        if x.ndim != 1 or x.dtype != np.float32:
+            raise SystemExit('%s holds %s %s: a float32 array [N] is expected' % (path, x.dtype, x.shape))
+        return x
+    return read_wav(path)
+
+
+def write_outputs(prefix, out, as_npy):
+    paths = []
+    for k, row in enumerate(np.asarray(out)):
+        path = '%s_%d.%s' % (prefix, k, 'npy' if as_npy else 'wav')
+        if as_npy:
+            np.save(path, np.asarray(row, np.float32))
+        else:
+            write_wav(path, row)
+        paths.append(path)
+    return paths
+
+
+def main(argv=None):
+    args = build_parser().get_args(argv)
+    if 'pretraining' in args.sortofmodel:
+        raise SystemExit('--sortofmodel %s: a pretraining model separates with masks made from the clean sources; a recording comes '
+                         'without them' % args.sortofmodel)
+    x = read_input(args.input)
+    if x.shape[0] < 1:
+        raise SystemExit('%s is empty' % args.input)
+    from experiments.evaluation.eval import pick
+    inferencer, sep = pick(args.sortofmodel)
+    tr = inferencer(sep, 'inference', **vars(args))
+    model = tr.prepare_inference()
+    with tr.graph.as_default():
+        out = model.separate_recording(x, hop=args.hop).cpu().numpy()
+    paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'))
+    print('\n'.join(paths))
+    return paths
+
+
+if __name__ == '__main__':
+    main()

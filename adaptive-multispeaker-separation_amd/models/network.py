@@ -507,14 +507,17 @@ class Network(object):
     def _inputs_of(self, run):
         return [(n, n.value(run)) for n in (self.x_mix, self.x_non_mix, self.I)]
 
-    def _eval_guarded(self, feed_dict, fn, training=False):
+    def _eval_guarded(self, feed_dict, fn, training=False, inputs=None):
         """fn(run) without gradients; the same batch again on the per-step kernels when a ring launch gave up (one host sync: every
-        caller reads its results on the host anyway)."""
+        caller reads its results on the host anyway).  inputs: (node, tensor) pairs that stand in for what the input pipeline would
+        deliver (infer_chunks); a repeated batch sees the same tensors."""
         # a word that is ALREADY set belongs to an earlier (training) launch whose owner has yet to handle it (Trainer.train checks
         # right after the step): it is not this evaluation's to clear -- the batch is evaluated on the per-step kernels and the word
         # stays up
         pre = K.LSTM_RING != '0' and self._ring_error_any()
         run = self._feeds(feed_dict, training)
+        for n, t in inputs or ():
+            run.cache[id(n)] = t
         if not pre:
             with torch.no_grad():
                 out = fn(run)
@@ -571,6 +574,61 @@ class Network(object):
 
     def infer(self, feed_dict, step):
         return self._eval_guarded(feed_dict, lambda run: [self.x_mix.value(run), self.x_non_mix.value(run), self.output.value(run)])
+
+    # ---- whole recordings: chunk, separate every chunk, track the outputs across the chunk borders, cross-fade
+    def _refuse_unless_separating(self):
+        if getattr(self, 'output', None) is None:
+            raise ValueError('this model has no `output`: build it with an inference recipe (utils/trainer.py)')
+        if getattr(self, 'pretraining', False):
+            raise ValueError('a pretraining model separates with masks made from the clean sources (Adapt.separator): it cannot '
+                             'separate a recording that comes without them')
+
+    def infer_chunks(self, mix, batch_size=None):
+        """mix [C, L] -> est [C, S, L]: `output` for every chunk, batch_size chunks per pass (default: the model's batch size).  The clean
+        sources and the speaker indices a training pass would read are fed as zeros.  A short last batch is filled up with copies of
+        its last chunk, which are dropped again: every pass has the same shape and the same k-means seed-draw pattern."""
+        self._refuse_unless_separating()
+        B = int(batch_size or self.args['batch_size'])
+        if mix.dim() != 2 or mix.shape[1] != self.args['chunk_size']:
+            raise ValueError('infer_chunks: chunks of %s samples for a model built with chunk_size %d'
+                             % (tuple(mix.shape)[1:], self.args['chunk_size']))
+        if B < 1 or mix.shape[0] < 1:
+            raise ValueError('infer_chunks: needs at least one chunk and a batch size of at least 1')
+        C, L = mix.shape
+        xn = torch.zeros((B, self.S, L), dtype=mix.dtype, device=mix.device)
+        ind = torch.zeros((B, self.S), dtype=torch.int32, device=mix.device)
+        est = None
+        for b0 in range(0, C, B):
+            xm = mix[b0:b0 + B]
+            n = xm.shape[0]
+            if n < B:
+                xm = torch.cat([xm, xm[-1:].expand(B - n, L)], dim=0)
+            ins = [(self.x_mix, xm.contiguous()), (self.x_non_mix, xn), (self.I, ind)]
+            out = self._eval_guarded({}, lambda run: self.output.value(run), inputs=ins)
+            if est is None:
+                if tuple(out.shape) != (B, self.S, L):
+                    # (an STFT recipe returns the samples its frames cover: chunk_size must be window_size + k * hop_size)
+                    raise ValueError('infer_chunks: `output` is %s, expected [%d, %d, %d]: the model must return every sample of a '
+                                     'chunk' % (tuple(out.shape), B, self.S, L))
+                est = torch.empty((C, self.S, L), dtype=out.dtype, device=out.device)
+            est[b0:b0 + n] = out[:n]
+        return est
+
+    def separate_recording(self, x, hop=None, batch_size=None):
+        """x [N] (a tensor or anything numpy takes) -> out [S, N] on the device: chunks of the model's chunk_size, `hop` apart (default
+        half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h)."""
+        from ams_hip import stitch as St
+        self._refuse_unless_separating()
+        L = int(self.args['chunk_size'])
+        H = St.default_hop(L) if hop is None else int(hop)
+        St.check_geometry(L, H)
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
+        if x.dim() != 1 or x.shape[0] < 1:
+            raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
+        est = self.infer_chunks(St.chunks(x, L, H), batch_size)
+        return St.stitch(est, x.shape[0], H)[0]
 
     def improvement(self, feed_dict, step):
         return self._eval_guarded(feed_dict, lambda run: [self.x_mix.value(run), self.x_non_mix.value(run), self.sdr_imp.value(run)])

@@ -203,6 +203,19 @@ class Trainer(object):
         self.tfds = tfds
         return dist, tfds
 
+    def prepare_inference(self):
+        """The model of an inference recipe without a dataset: the three inputs are placeholders nobody feeds, whoever runs the model
+        supplies them (Network.infer_chunks / separate_recording do).  Returns the model; evaluate it inside self.graph.as_default()."""
+        from ams_hip.graph import Placeholder
+        self._open()
+        with self.graph.as_default():
+            with self.graph.variable_scope('recording'):
+                mix, non_mix, ind = Placeholder('mix'), Placeholder('non_mix'), Placeholder('ind')
+            # (as _pipeline_args: a checkpoint's params file may say pipeline = True, and Network.load keeps what the file says)
+            self.args.update({"mix": mix, "non_mix": non_mix, "ind": ind, "pipeline": True, "tot_speakers": 251})
+            self.build()
+        return self.model
+
     def inference(self):
         dist = self._open()
         with self.graph.as_default():
