@@ -268,7 +268,7 @@ class Dense(Function):
             adu = ops.amax_of(du2)                               # the loss kernel that wrote dU left its bound (ops.dpcl_loss_bwd_u)
             am_dx, am_dw = (adu, ctx.amax[1]), (ctx.amax[0], adu)
         if OVERLAP.usable(W, b) and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            dx = ops.backward_product(du2, W, am_dx, W).view(x.shape) if ctx.needs_input_grad[0] else None
+            dx = ops.backward_product(du2, W, am_dx, (W,)).view(x.shape) if ctx.needs_input_grad[0] else None
             s = OVERLAP.fork(x2, du2)
             Nw = W.shape[1]
             cuts = _dw_cuts(Nw) if (ctx.needs_input_grad[0] and W.grad.stride(0) == Nw) else [(0, Nw)]
@@ -295,7 +295,7 @@ class Dense(Function):
             if len(cuts) == 1:
                 OVERLAP.ready(W, b)
             return dx, None, None
-        dx = ops.backward_product(du2, W, am_dx, W).view(x.shape) if ctx.needs_input_grad[0] else None
+        dx = ops.backward_product(du2, W, am_dx, (W,)).view(x.shape) if ctx.needs_input_grad[0] else None
         dW = ops.gemm(x2, du2, transA=True, amax=am_dw) if ctx.needs_input_grad[1] else None
         db = ops.colsum(du2) if ctx.needs_input_grad[2] else None
         return dx, dW, db

@@ -249,9 +249,51 @@ def _frozen(*ts):
 
 
 def drop_frozen_derivatives(t):
-    for k in ('_ams_amax_cache', '_ams_wcat', '_ams_wcat_amax', '_ams_kbound', '_ams_bcat', '_ams_ps_w', '_ams_ps_dx'):
-        if hasattr(t, k):
-            delattr(t, k)
+    if hasattr(t, '_ams_derived'):
+        del t._ams_derived
+
+
+def set_frozen(t, on):
+    """Set or clear the mark _frozen() reads.  Either way what was derived from `t` under the other rule is dropped."""
+    drop_frozen_derivatives(t)
+    if on:
+        t._ams_frozen = True
+    elif hasattr(t, '_ams_frozen'):
+        del t._ams_frozen
+
+
+def derived(owners, name, make, key=(), keep='pass'):
+    """The tensor `name` derived from the weight tensor(s) `owners` (bounds, gathered kernels, concatenated biases, operand images): THE
+    cache and THE staleness rule for all of them.  The value lives in one dict on owners[0] and is valid only while
+      - `key` (plain values: shapes, addresses, ids -- no tensors) is equal,
+      - the other owners are the same objects, and
+      - it was made in this evaluation pass (PASS[0]) or every owner is frozen (_frozen: nothing writes them between passes).
+    Otherwise make(old) makes it, `old` being the stale value or None: a bound is refreshed IN PLACE (absmax(..., out=old)), because a
+    captured step holds its address.  keep='frozen': nothing is stored unless every owner is frozen (what would otherwise be rebuilt in
+    every call keeps dying with the pass that made it).  set_frozen() and drop_frozen_derivatives() drop the dict."""
+    if not isinstance(owners, tuple):                            # (a bare owner: what tests hand to the product wrappers)
+        owners = (owners,)
+    d = getattr(owners[0], '_ams_derived', None)
+    e = d.get(name) if d is not None else None
+    if e is not None and e[1] == key and len(e[2]) == len(owners):
+        fresh = e[0] == PASS[0]
+        for a, b in zip(e[2], owners):                           # (one plain loop: this runs for every product of an eager pass)
+            if a is not b or not (fresh or getattr(b, '_ams_frozen', False)):
+                break
+        else:
+            return e[3]
+    val = make(e[3] if e is not None else None)
+    if keep == 'pass' or _frozen(*owners):
+        if d is None:
+            owners[0]._ams_derived = d = {}
+        d[name] = (PASS[0], key, owners, val)
+    return val
+
+
+def derived_entry(t, name):
+    """What derived() holds under `name` on `t` (valid or not), else None."""
+    e = getattr(t, '_ams_derived', {}).get(name)
+    return None if e is None else e[3]
 
 
 class _ParamSource(object):
@@ -288,10 +330,7 @@ def param_amax(W):
         elif src.event is not None:                              # measured on the side stream: every consuming stream waits once
             _await_pass_side()
         return src.bound
-    c = getattr(W, '_ams_amax_cache', None)
-    if c is None or (c[0] != PASS[0] and not _frozen(W)):
-        W._ams_amax_cache = c = (PASS[0], absmax(W.detach(), out=c[1] if c is not None else None))
-    return c[1]
+    return derived((W,), 'amax', lambda old: absmax(W.detach(), out=old))
 
 
 class _PassSide(object):
@@ -710,15 +749,11 @@ def gemm_ps(a_img, b_img, K, amax, bias=None, out=None, ldc=None, label=''):
     return out
 
 
-def _ps_weight_image(W2, amax_w, owner):
+def _ps_weight_image(W2, amax_w, owners):
     """PS32 image of W2^T, cut once per evaluation pass (inside a captured step: by every replay) and kept across passes for frozen
-    weights (Network.freeze_weights; dropped with the other derived tensors by drop_frozen_derivatives): cached on `owner`."""
-    c = getattr(owner, '_ams_ps_w', None)
-    if (c is not None and c[1] == W2.data_ptr() and c[2] == tuple(W2.shape) and c[3] is amax_w and (c[0] == PASS[0] or _frozen(owner))):
-        return c[4]
-    img = ps_pack_cols(W2, amax_w)
-    owner._ams_ps_w = (PASS[0], W2.data_ptr(), tuple(W2.shape), amax_w, img)
-    return img
+    weights (derived()); `owners`: every weight tensor W2 was made from."""
+    # (the entry holds the bound the image was cut with: the id in its key stays taken)
+    return derived(owners, 'ps_w', lambda old: (ps_pack_cols(W2, amax_w), amax_w), key=(W2.data_ptr(), W2.shape, id(amax_w)))[0]
 
 
 def forward_product_presplit(M, N, K, out, bias, amax, label, ldc):
@@ -731,7 +766,7 @@ def forward_product_presplit(M, N, K, out, bias, amax, label, ldc):
             and load().ams_gemm_get_arith() != 0)
 
 
-def forward_product(x2, W2, bias, out, amax, label, owner, ldc=None):
+def forward_product(x2, W2, bias, out, amax, label, owners, ldc=None):
     """out[M, N] = x2 [M, K] . W2 [K, N] + bias: the forward products of the path (BLSTM input projection, Conv1D).  From pre-split
     operand images (csrc/gemm_ps.hip) where forward_product_presplit() says so -- x2's image is cut here, W2's once per pass (kept across
     passes for frozen weights); otherwise ams_gemm_f32."""
@@ -744,7 +779,7 @@ def forward_product(x2, W2, bias, out, amax, label, owner, ldc=None):
     if not forward_product_presplit(M, N, K, out, bias, amax, label, ldc):
         return gemm(x2, W2, bias=bias, out=out, M=M, N=N, K=K, lda=x2.stride(0), ldb=W2.stride(0), ldc=ldc, label=label, amax=amax)
     a_img = ps_pack_rows(x2, amax[0])
-    b_img = _ps_weight_image(W2, amax[1], owner)
+    b_img = _ps_weight_image(W2, amax[1], owners)
     return gemm_ps(a_img, b_img, K, amax, bias=bias, out=out, ldc=ldc, label=label)
 
 
@@ -753,18 +788,13 @@ def forward_product(x2, W2, bias, out, amax, label, owner, ldc=None):
 DX_PS = _os.environ.get('AMS_GEMM_DX_PS', '1') != '0'
 
 
-def _ps_dx_weight_image(W2, amax_w, owner):
+def _ps_dx_weight_image(W2, amax_w, owners):
     """PS32 image of W2 [N, K] itself (the B operand of dU . W2^T: no transpose), cut once per pass and kept across passes for frozen
-    weights; cached on `owner` beside (not in) the forward products' image of W2^T."""
-    c = getattr(owner, '_ams_ps_dx', None)
-    if (c is not None and c[1] == W2.data_ptr() and c[2] == tuple(W2.shape) and c[3] is amax_w and (c[0] == PASS[0] or _frozen(owner))):
-        return c[4]
-    img = ps_pack_rows(W2, amax_w)
-    owner._ams_ps_dx = (PASS[0], W2.data_ptr(), tuple(W2.shape), amax_w, img)
-    return img
+    weights (derived()), beside (not in) the forward products' image of W2^T."""
+    return derived(owners, 'ps_dx', lambda old: (ps_pack_rows(W2, amax_w), amax_w), key=(W2.data_ptr(), W2.shape, id(amax_w)))[0]
 
 
-def backward_product(dU2, W2, amax, owner, out=None, label=''):
+def backward_product(dU2, W2, amax, owners, out=None, label=''):
     """out [M, N] = dU2 [M, K] . W2 [N, K]^T: the input gradients of the dense layer and of a BLSTM layer's input projection.  From a
     pre-split image of W2 (cut once per pass, kept for frozen weights) with dU2 cut inside the product where both bounds are at hand,
     fp16x3 is not denied for this product class (the key of the in-product form), no audit is in progress, no residency cap, and the
@@ -785,7 +815,7 @@ def backward_product(dU2, W2, amax, owner, out=None, label=''):
         # (the last two: where the in-product form is fp16x3 -- 16-byte fetches -- on the same 128 x 256 tile, csrc/gemm.hip: launch,
         # x6_choose_cfg, and so gives the same bits)
         return gemm(dU2, W2, transB=True, out=out, M=M, N=N, K=K, lda=lda, ldb=W2.stride(0), ldc=ldc, label=label, amax=amax)
-    b_img = _ps_dx_weight_image(W2, amax[1], owner)
+    b_img = _ps_dx_weight_image(W2, amax[1], owners)
     nb = lib.ams_gemm_ps_a_workspace_bytes(M, N, K)
     ws = _ws(nb, dU2) if nb else None
     ev = PROFILE.begin() if PROFILE.enabled else None
@@ -971,36 +1001,21 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
         raise AmsError('blstm: the two direction kernels must share one row stride')
     x2 = x.view(B * T, D)
     frozen = _frozen(Kf, Kb, bf, bb)
-    if frozen:                                                   # inference recipes: gathered once, not in every pass
-        c = getattr(Kf, '_ams_wcat', None)
-        if c is None or c[0] is not Kb or c[1] != D:
-            Kf._ams_wcat = c = (Kb, D, blstm_wcat(Kf, Kb, D))
-        Wcat = c[2]
-    else:
-        Wcat = blstm_wcat(Kf, Kb, D)
+    # (keep='frozen': inference recipes gather once, not in every pass)
+    Wcat = derived((Kf, Kb), 'wcat', lambda old: blstm_wcat(Kf, Kb, D), key=(D,), keep='frozen')
     u_amax = amax[1] if amax is not None else None               # the caller's weight bound covers the recurrent kernels too
     if amax is None and F16X3 and x.is_cuda:
         if frozen:
             # ONE bound over both whole kernels, measured once: the projection AND the ring's recurrent product run as fp16x3
-            c = getattr(Kf, '_ams_kbound', None)
-            if c is None or c[0] is not Kb:
-                Kf._ams_kbound = c = (Kb, torch.maximum(absmax(Kf), absmax(Kb)))
-            amax, u_amax = (amax_of(x), c[1]), c[1]
+            u_amax = derived((Kf, Kb), 'kbound', lambda old: torch.maximum(absmax(Kf), absmax(Kb)), keep='frozen')
+            amax = (amax_of(x), u_amax)
         else:
             # no optimizer, hence no common bound of the two kernels: the gathered [D, 8H] matrix is measured once per pass
-            c = getattr(Kf, '_ams_wcat_amax', None)
-            if c is None or c[0] != PASS[0]:
-                Kf._ams_wcat_amax = c = (PASS[0], absmax(Wcat, out=c[1] if c is not None else None))
-            amax = (amax_of(x), c[1])
+            amax = (amax_of(x), derived((Kf, Kb), 'wcat_amax', lambda old: absmax(Wcat, out=old)))
     if _twin(bf, bb):
         bias = torch.as_strided(bf, (8 * H,), (1,))
-    elif frozen:
-        c = getattr(bf, '_ams_bcat', None)
-        if c is None or c[0] is not bb:
-            bf._ams_bcat = c = (bb, torch.cat([bf, bb]))
-        bias = c[1]
     else:
-        bias = torch.cat([bf, bb])
+        bias = derived((bf, bb), 'bcat', lambda old: torch.cat([bf, bb]), keep='frozen')
     G = torch.empty((B, T, 2, 4 * H), dtype=torch.float32, device=x.device)
     # hoisted input projection of BOTH directions as ONE MFMA GEMM [B*T, D] x [D, 8H]: the two [D,4H] halves of the TF
     # kernels are gathered side by side (a 2 x D x 4H copy) so N = 8H gives 19 x 40 = 760 tiles = 2.97 per CU instead of
@@ -1009,7 +1024,7 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
     out = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
     # ring recurrence: plane 0 = c_t (what every backward reads as `cst`), plane 1 = tanh(c_t) for the backward ring
     cst = torch.empty(((2, B, T, 2, H) if nring else (B, T, 2, H)), dtype=torch.float32, device=x.device)
-    blstm_input_projection(x2, Wcat, bias, G.view(B * T, 8 * H), amax, Kf)
+    blstm_input_projection(x2, Wcat, bias, G.view(B * T, 8 * H), amax, (Kf, Kb))
     if nring:
         sync, pre0 = _ring_sync(nring, x)
         check(lib.ams_blstm_ring_fwd(_p(G), _p(out), _p(cst[0]), _p(cst[1]), _p(Kf[D:]), _p(Kb[D:]), ldu,
@@ -1022,7 +1037,7 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
     return out, G, cst
 
 
-def blstm_input_projection(x2, Wcat, bias, G2, amax, owner):
+def blstm_input_projection(x2, Wcat, bias, G2, amax, owners):
     """G2 [M, 8H] = x2 [M, D] . Wcat [D, 8H] + bias: the hoisted input projection of both directions of a BLSTM layer, in whichever
     form applies -- from pre-split images (forward_product_presplit), the product itself on aligned rows, or, for an input width that is
     not a multiple of 4, a zero-padded copy.  All three are ONE product class for the range audit, keyed by the unpadded shape (K = D):
@@ -1037,7 +1052,7 @@ def blstm_input_projection(x2, Wcat, bias, G2, amax, owner):
         Wp[:D].copy_(Wcat)
         return gemm(_padded_rows(x2, Dp), Wp, bias=bias, out=G2, M=M, N=N, K=Dp, lda=Dp, ldb=N, ldc=N, label=label, amax=amax,
                     key=('gemm', label, M, N, D, False, False))
-    return forward_product(x2, Wcat, bias, G2, amax, label, owner)
+    return forward_product(x2, Wcat, bias, G2, amax, label, owners)
 
 
 def dense_fwd(x, W, b, amax=None):
@@ -1046,7 +1061,7 @@ def dense_fwd(x, W, b, amax=None):
     if x2.stride(1) != 1:
         x2 = x2.contiguous()            # (a transposed view: the product reads dense rows)
     out = torch.empty((x2.shape[0], W.shape[1]), dtype=torch.float32, device=x.device)
-    return forward_product(x2, W, b, out, amax, '', W).view(x.shape[:-1] + (W.shape[1],))
+    return forward_product(x2, W, b, out, amax, '', (W,)).view(x.shape[:-1] + (W.shape[1],))
 
 
 def blstm_wcat(Kf, Kb, D):
@@ -1168,7 +1183,7 @@ def blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=None):
     M = B * T
     Wcat = blstm_wcat(Kf, Kb, D)
     dx = torch.empty((B, T, D), dtype=torch.float32, device=G.device)
-    backward_product(G.view(M, 8 * H), Wcat, amax, Kf, out=dx.view(M, D))
+    backward_product(G.view(M, 8 * H), Wcat, amax, (Kf, Kb), out=dx.view(M, D))
     return dx
 
 

@@ -14,6 +14,9 @@ from . import ops
 class FlatOptimizer(object):
     def __init__(self, variables, kind, learning_rate, decay_epoch, gradient_clip, dist=None):
         self.vars = list(variables)
+        if any(ops._frozen(v) for v in self.vars):
+            # (what ops.derived() keeps for a frozen tensor would go stale behind the optimizer kernels: ops.set_frozen(v, False) first)
+            raise ops.AmsError('FlatOptimizer: a parameter carries the frozen mark (Network.freeze_weights)')
         self.kind = kind
         self.base_lr = float(learning_rate)
         self.decay_epoch = int(decay_epoch)

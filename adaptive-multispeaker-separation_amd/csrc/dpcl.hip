@@ -12,6 +12,7 @@
 // VALU matvec with the small matrices fetched through the scalar cache; points are transposed through LDS so
 // global traffic stays float4-coalesced.
 #include "common.h"
+#include "split.h"
 
 // timing anatomy builds (WRONG results): 1 = no MFMAs, 2 = no norm / no epilogue arithmetic, 4 = no global loads, 8 = no global stores
 #ifndef AMS_DPCL_AMAX
@@ -419,18 +420,6 @@ __global__ __launch_bounds__(256) void dpcl_gram_u_kernel(const float* __restric
 // Two threads per point do norm and cut together: each sums 20 features, the pair meets by DPP, and pairs of neighbouring points swap
 // what the other one writes (DPP again), so every thread writes ten dwords per plane.  128 points per slab, one 32-point group per
 // wave; everything around it (label counts, chunk partials in chunk order, the in-launch finish) is dpcl_gram_u_kernel's.
-typedef _Float16 dp_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 dp_f16x2 __attribute__((ext_vector_type(2)));
-typedef float dp_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned dp_pk_f16(float a, float b) {
-    const dp_f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, dp_f16x2));
-}
-__device__ __forceinline__ void dp_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = dp_pk_f16(a, b);
-    const dp_f16x2 h = __builtin_bit_cast(dp_f16x2, hi);
-    lo = dp_pk_f16(a - (float)h[0], b - (float)h[1]);
-}
 __device__ __forceinline__ float dp_lane_xor1(float v) {      // quad_perm [1,0,3,2]
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
 }
@@ -532,7 +521,7 @@ __global__ __launch_bounds__(256) void dpcl_gram_u16_kernel(const float* __restr
                 const float give = odd ? v[k] : v[QF + k];      // ... and what the neighbouring point's thread writes
                 const float got = dp_lane_xor2(give);
                 unsigned hi, lo;
-                dp_split2(odd ? got : own, odd ? own : got, hi, lo);           // (even point, odd point)
+                split2h(odd ? got : own, odd ? own : got, hi, lo);           // (even point, odd point)
                 *reinterpret_cast<unsigned*>(wbase + k * HP) = hi;
                 *reinterpret_cast<unsigned*>(wbase + k * HP + Z * HP) = lo;
             }
@@ -542,7 +531,7 @@ __global__ __launch_bounds__(256) void dpcl_gram_u16_kernel(const float* __restr
                     const float own = zt[pnt2 * ZP + E + s] * sd;
                     const float got = dp_lane_xor2(own);
                     unsigned hi, lo;
-                    dp_split2(own, got, hi, lo);
+                    split2h(own, got, hi, lo);
                     if (!odd) {
                         *reinterpret_cast<unsigned*>(zh + (E + s) * HP + (pnt2 >> 1) * 4) = hi;
                         *reinterpret_cast<unsigned*>(zh + (E + s) * HP + (pnt2 >> 1) * 4 + Z * HP) = lo;
@@ -561,11 +550,11 @@ __global__ __launch_bounds__(256) void dpcl_gram_u16_kernel(const float* __restr
         {
             // wave w: points 32 w .. 32 w + 31; lane (feature e_lo of a tile, points 8 slot .. 8 slot + 7)
             const unsigned char* const rb = zh + e_lo * HP + (32 * wave + 8 * slot) * 2;
-            dp_f16x8 a[NT][2];
+            f16x8_t a[NT][2];
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) a[ti][p] = *reinterpret_cast<const dp_f16x8*>(rb + ti * 16 * HP + p * Z * HP);
+                for (int p = 0; p < 2; ++p) a[ti][p] = *reinterpret_cast<const f16x8_t*>(rb + ti * 16 * HP + p * Z * HP);
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -1038,14 +1027,12 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
                 }
     }
 #if AMS_DPCL_BWD_F16
-    // fp16x3 (csrc/gemm.hip): M scaled by a power of two from its own maximum and split exactly into two fp16 terms, once per workgroup;
+    // fp16x3 (csrc/split.h): M scaled by a power of two from its own maximum and split exactly into two fp16 terms, once per workgroup;
     // z (|u / |u|| <= 1, labels 0 / 1) scaled by 2^13 and split per group.  A lane's four k-slots of block j are exactly its A / B
     // fragment of a v_mfma_f32_16x16x16_f16, blocks 0 and 1 together those of a 16x16x32: 18 MFMAs of ~16 cycles per group of 16 points
     // instead of 36 v_mfma_f32_16x16x4_f32 of 32 (38 us of matrix pipe per launch at 64 x 20480 points).
-    typedef _Float16 dh8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 dh4 __attribute__((ext_vector_type(4)));
-    dh8 a8[NT][2];                                  // [feature tile][plane hi / lo], k-blocks 0 and 1
-    dh4 a4[NT][2];                                  //                                 k-block 2
+    f16x8_t a8[NT][2];                              // [feature tile][plane hi / lo], k-blocks 0 and 1
+    f16x4_t a4[NT][2];                              //                                 k-block 2
     float m_inv;
     {
         float mx = 0.f;
@@ -1057,6 +1044,7 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
                 for (int ft = 0; ft < NT; ++ft) mx = fmaxf(mx, fabsf(am[j][i][ft]));
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        // csrc/split.h: f16_scale2, written out: through the call hipcc schedules this kernel differently (same values)
         const int ex = (int)((__float_as_uint(mx) >> 23) & 0xffu);
         const int se = 127 + 13 - (ex - 127);
         const bool ok = ex != 0 && ex != 255 && se >= 1 && se <= 253;
@@ -1127,8 +1115,8 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
 #endif
 #if AMS_DPCL_BWD_F16
         {
-            dh8 z8[2];
-            dh4 z4[2];
+            f16x8_t z8[2];
+            f16x4_t z4[2];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float v = z[e >> 2][e & 3] * 8192.0f;

@@ -18,6 +18,7 @@
 // Split-K (gridDim.z) writes fp32 partial slabs to a caller workspace; a second kernel reduces them in
 // fixed order (deterministic) and applies bias / accumulate.
 #include "common.h"
+#include "split.h"
 #include <stdlib.h>
 #include <atomic>
 #include <type_traits>
@@ -656,10 +657,6 @@ __global__ __launch_bounds__(256, AMS_GEMM_WPE) void gemm_f32_kernel(GemmArgs g)
 // 232c519).  The kernel draws the board's power limit (1385-1393 W at 2135 MHz; its MFMA-only stream 1050 W at 2400 MHz) and gains
 // 0-4 % with the split arithmetic compiled out: at that limit its run time is the energy of a product, not its instruction schedule
 // (DESIGN.md 4.0).
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 #ifndef AMS_X6_DBG
 #define AMS_X6_DBG 0        // timing anatomy only (WRONG results): 1 no split arithmetic, 2 no LDS writes, 4 no MFMAs, 8 no LDS reads, 16 no fetch in the loop
 #endif
@@ -674,43 +671,12 @@ constexpr int x6_bm(int) { return 128; }
 constexpr int x6_bn(int cfg) { return cfg == 3 ? 256 : 128; }
 constexpr int x6_lds(int cfg) { return x6_oper(x6_bm(cfg)) + x6_oper(x6_bn(cfg)); }
 
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {           // v_cvt_pk_bf16_f32: a -> bits 0..15, b -> bits 16..31
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// fp16x3 (round 3): two fp16 planes per operand instead of three bf16 planes, three products instead of six.
-//   a * s = h0 + h1 + e,  h0 = fp16(a s),  h1 = fp16(a s - h0),  |e| <= 2^-22 |a s|   (both conversions round to nearest; h0 * h0' is exact in f32)
-//   a.b ~ [h0.h0' + (h0.h1' + h1.h0')] / (s s')   -- dropped: h1.h1' (2^-22) and e: the same 2^-22 level as the f32 accumulation itself
-// s = 2^(13 - floor(log2(amax))): the largest operand entry lands in [2^13, 2^14) (fp16 overflows at 65504), entries down to amax * 2^-17
-// keep all 22 bits, smaller ones an absolute error of amax * 2^-39.  bf16x6 needs no scale (bf16 has the f32 exponent) and stays the
-// arithmetic of every launch that does not supply the bounds.
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_f16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-}
-__device__ __forceinline__ void split2h(float a, float b, unsigned& hi, unsigned& mid) {
-    hi = pk_f16(a, b);
-    const f16x2_t h = __builtin_bit_cast(f16x2_t, hi);
-    mid = pk_f16(a - (float)h[0], b - (float)h[1]);
-}
-// 2^(13 - floor(log2(amax))) for a finite positive amax; 1 for 0, denormals, Inf and NaN (which then propagate as they would in f32)
-__device__ __forceinline__ float f16_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    if (e == 0 || e == 255) return 1.0f;
-    const int se = 127 + 13 - (e - 127);            // biased exponent of the scale
-    return (se >= 1 && se <= 254) ? __uint_as_float((unsigned)se << 23) : 1.0f;
-}
-__device__ __forceinline__ void split3(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
+// The operand cuts are csrc/split.h's (pk_bf16, pk_f16, split2h, split3, f16_scale; the fp16x3 error model is stated there).
+__device__ __forceinline__ void x6_split3(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
 #if AMS_X6_DBG & 1
     hi = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u); mid = hi; lo = hi; return;
 #endif
-    hi = pk_bf16(a, b);
-    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
-    mid = pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(mid << 16), sb = rb - __uint_as_float(mid & 0xffff0000u);
-    lo = pk_bf16(sa, sb);
+    split3(a, b, hi, mid, lo);
 }
 // LDS row of operand row n (0..R-1) for m/n-contiguous sources: the four rows a thread's float4 covers go to four R/4-row blocks,
 // rotated by 4 rows per block (read groups {0-3,12-15,20-27} / {4-11,16-19,28-31} of ds_read_b128 then touch 16 different slots).
@@ -727,18 +693,6 @@ __device__ long long g_x6_stamp[1024 * 8 * 8];
 #else
 #define X6_STAMP(ph) do { } while (0)
 #endif
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-// Raw buffer accesses with aux bit 16 = sc1: stores write through to the memory side, loads bypass this CU's L1 -- the publish form of
-// MI355X_MICROARCH.md ("publish-large": sc1 payload -> s_waitcnt vmcnt(0) -> agent-scope flag, sc1 loads on the reader)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t x6_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 ld16_sc1(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16));
-}
-__device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t rs, unsigned off, float4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), rs, off, 0, 16);
-}
 
 template <int AMODE, int BMODE, int CFG, int EPI, bool SEP, bool F16>
 // PERSISTENT over work items (round 3): the grid is at most one resident set of workgroups (ams_gemm launch: 256 CUs x the
@@ -972,10 +926,10 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                 split2h(rv[2 * h + 1].z * sc, rv[2 * h + 1].w * sc, hi.w, mid.w);
                 lo = hi;
             } else {
-            split3(rv[2 * h].x, rv[2 * h].y, hi.x, mid.x, lo.x);
-            split3(rv[2 * h].z, rv[2 * h].w, hi.y, mid.y, lo.y);
-            split3(rv[2 * h + 1].x, rv[2 * h + 1].y, hi.z, mid.z, lo.z);
-            split3(rv[2 * h + 1].z, rv[2 * h + 1].w, hi.w, mid.w, lo.w);
+            x6_split3(rv[2 * h].x, rv[2 * h].y, hi.x, mid.x, lo.x);
+            x6_split3(rv[2 * h].z, rv[2 * h].w, hi.y, mid.y, lo.y);
+            x6_split3(rv[2 * h + 1].x, rv[2 * h + 1].y, hi.z, mid.z, lo.z);
+            x6_split3(rv[2 * h + 1].z, rv[2 * h + 1].w, hi.w, mid.w, lo.w);
             }
             unsigned char* p = base + kgrp * PL + (krow + (NT / 4) * h) * 16;
             if (AMS_X6_DBG & 2) { asm volatile("" :: "v"(hi.x ^ hi.y ^ hi.z ^ hi.w ^ mid.x ^ mid.y ^ mid.z ^ mid.w ^ lo.x ^ lo.y ^ lo.z ^ lo.w)); continue; }
@@ -997,8 +951,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                 split2h(comp4(rv[2], j) * sc, comp4(rv[3], j) * sc, hi.y, mid.y);
                 lo = hi;
             } else {
-            split3(comp4(rv[0], j), comp4(rv[1], j), hi.x, mid.x, lo.x);
-            split3(comp4(rv[2], j), comp4(rv[3], j), hi.y, mid.y, lo.y);
+            x6_split3(comp4(rv[0], j), comp4(rv[1], j), hi.x, mid.x, lo.x);
+            x6_split3(comp4(rv[2], j), comp4(rv[3], j), hi.y, mid.y, lo.y);
             }
             const int slot = j == 0 ? slot0 : j == 1 ? slot1 : j == 2 ? slot2 : slot3;
             unsigned char* p = base + (kb >> 1) * PL + slot * 16 + (kb & 1) * 8;
@@ -1159,7 +1113,7 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
             __syncthreads();
             for (int wp = sk_w - 1; wp >= 0 && (wp + 1) * sk_U / sk_Gx > tile_start; --wp) {
                 const int src = wp * 8 + sk_x;
-                const __amdgpu_buffer_rsrc_t rs = x6_rsrc(g0.sk_slots + (long)src * g0.sk_slot_floats, (unsigned)g0.sk_slot_floats * 4u);
+                const __amdgpu_buffer_rsrc_t rs = make_rsrc(g0.sk_slots + (long)src * g0.sk_slot_floats, (unsigned)g0.sk_slot_floats * 4u);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1220,7 +1174,7 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
             // PERSIST form the next segment's first k-tile is in flight here: its loads are older than these stores and vmcnt retires
             // in order, so the wait below covers both -- the stash that follows would have waited for them anyway.
             const int me = (int)blockIdx.x;
-            const __amdgpu_buffer_rsrc_t rs = x6_rsrc(g0.sk_slots + (long)me * g0.sk_slot_floats, (unsigned)g0.sk_slot_floats * 4u);
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(g0.sk_slots + (long)me * g0.sk_slot_floats, (unsigned)g0.sk_slot_floats * 4u);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll

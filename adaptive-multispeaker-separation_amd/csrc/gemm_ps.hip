@@ -28,15 +28,12 @@
 // (models/network.py::_train_graphed).  -DAMS_PS_SLEEP=N (s_sleep N behind every group of four MFMAs) is the probe that showed the clock
 // coming back as the duty goes down (profiles/r06_f_step_clock_and_forward_product_form.txt); it is not a tuning knob.
 #include "common.h"
+#include "split.h"
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int PS_BK = 32, PS_BM = 128, PS_BN = 256, PS_NT = 512;
 constexpr int PS_A_BYTES = PS_BM * 128, PS_B_BYTES = PS_BN * 128, PS_STAGE = PS_A_BYTES + PS_B_BYTES;     // 16 KB + 32 KB
@@ -44,22 +41,6 @@ constexpr int PS_STAGES = 3;
 constexpr int PS_BIAS_OFF = PS_STAGES * PS_STAGE;                                                           // two 1 KB bias slices behind the stages
 constexpr int PS_LDS = PS_BIAS_OFF + 2 * 1024;                                                              // 146 KB
 
-__device__ __forceinline__ unsigned ps_pk_f16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-}
-__device__ __forceinline__ void ps_split2(float a, float b, unsigned& hi, unsigned& lo) {
-    hi = ps_pk_f16(a, b);
-    const f16x2_t h = __builtin_bit_cast(f16x2_t, hi);
-    lo = ps_pk_f16(a - (float)h[0], b - (float)h[1]);
-}
-// 2^(13 - floor(log2(amax))) for a finite positive amax; 1 for 0, denormals, Inf and NaN (the rule of csrc/gemm.hip: f16_scale)
-__device__ __forceinline__ float ps_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    if (e == 0 || e == 255) return 1.0f;
-    const int se = 127 + 13 - (e - 127);
-    return (se >= 1 && se <= 254) ? __uint_as_float((unsigned)se << 23) : 1.0f;
-}
 
 // ---- image writers ------------------------------------------------------------------------------------------------------------------
 // x [R, K] row-major (row pitch ldx floats) -> image rows of `pitch` bytes.  One thread per (row, group of 8 k): two float4 in, 16 B of
@@ -70,7 +51,7 @@ __global__ __launch_bounds__(256) void ps_pack_rows_kernel(const float* __restri
     const long id = (long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long)R * groups) return;
     const int r = (int)(id / groups), gq = (int)(id - (long)r * groups), k = gq * 8;
-    const float s = ps_scale(amax[0]);
+    const float s = f16_scale(amax[0]);
     float v[8];
     const float* row = x + (long)r * ldx;
     if (k + 8 <= K && ((((uintptr_t)(row + k)) & 15) == 0)) {
@@ -81,10 +62,10 @@ __global__ __launch_bounds__(256) void ps_pack_rows_kernel(const float* __restri
         for (int j = 0; j < 8; ++j) v[j] = (k + j < K) ? row[k + j] : 0.f;
     }
     uint4 hi, lo;
-    ps_split2(v[0] * s, v[1] * s, hi.x, lo.x);
-    ps_split2(v[2] * s, v[3] * s, hi.y, lo.y);
-    ps_split2(v[4] * s, v[5] * s, hi.z, lo.z);
-    ps_split2(v[6] * s, v[7] * s, hi.w, lo.w);
+    split2h(v[0] * s, v[1] * s, hi.x, lo.x);
+    split2h(v[2] * s, v[3] * s, hi.y, lo.y);
+    split2h(v[4] * s, v[5] * s, hi.z, lo.z);
+    split2h(v[6] * s, v[7] * s, hi.w, lo.w);
     unsigned char* p = img + (long)r * pitch + (k >> 5) * 128 + ((k & 31) >> 3) * 16;
     *reinterpret_cast<uint4*>(p) = hi;
     *reinterpret_cast<uint4*>(p + 64) = lo;
@@ -101,7 +82,7 @@ __global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restri
     const int n0 = blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int nl = threadIdx.x >> 2, kg = threadIdx.x & 3;
-    const float s = ps_scale(amax[0]);
+    const float s = f16_scale(amax[0]);
     const int kt_end = min((int)((K + 31) / 32), (int)(blockIdx.y + 1) * PS_PC_KT);
     float v[8];
     auto fetch = [&](int kt) {
@@ -121,10 +102,10 @@ __global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restri
         if (kt + 1 < kt_end) fetch(kt + 1);
         if (n0 + nl < N) {
             uint4 hi, lo;
-            ps_split2(t[kg * 8 + 0][nl] * s, t[kg * 8 + 1][nl] * s, hi.x, lo.x);
-            ps_split2(t[kg * 8 + 2][nl] * s, t[kg * 8 + 3][nl] * s, hi.y, lo.y);
-            ps_split2(t[kg * 8 + 4][nl] * s, t[kg * 8 + 5][nl] * s, hi.z, lo.z);
-            ps_split2(t[kg * 8 + 6][nl] * s, t[kg * 8 + 7][nl] * s, hi.w, lo.w);
+            split2h(t[kg * 8 + 0][nl] * s, t[kg * 8 + 1][nl] * s, hi.x, lo.x);
+            split2h(t[kg * 8 + 2][nl] * s, t[kg * 8 + 3][nl] * s, hi.y, lo.y);
+            split2h(t[kg * 8 + 4][nl] * s, t[kg * 8 + 5][nl] * s, hi.z, lo.z);
+            split2h(t[kg * 8 + 6][nl] * s, t[kg * 8 + 7][nl] * s, hi.w, lo.w);
             unsigned char* p = img + (long)(n0 + nl) * pitch + kt * 128 + kg * 16;
             *reinterpret_cast<uint4*>(p) = hi;
             *reinterpret_cast<uint4*>(p + 64) = lo;
@@ -148,17 +129,17 @@ __global__ __launch_bounds__(256) void ps_pack_conv_kernel(const float* __restri
     const int c = (int)(id / per_copy);
     const long rem = id - (long)c * per_copy;
     const int sgn = (int)(rem / lpp), t = (int)(rem - (long)sgn * lpp);
-    const float s = ps_scale(amax[0]);
+    const float s = f16_scale(amax[0]);
     const float* row = x + (long)sgn * L;
     const int i0 = c + 8 * t - pl;
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { const int i = i0 + j; v[j] = (i >= 0 && i < L) ? row[i] : 0.f; }
     uint4 hi, lo;
-    ps_split2(v[0] * s, v[1] * s, hi.x, lo.x);
-    ps_split2(v[2] * s, v[3] * s, hi.y, lo.y);
-    ps_split2(v[4] * s, v[5] * s, hi.z, lo.z);
-    ps_split2(v[6] * s, v[7] * s, hi.w, lo.w);
+    split2h(v[0] * s, v[1] * s, hi.x, lo.x);
+    split2h(v[2] * s, v[3] * s, hi.y, lo.y);
+    split2h(v[4] * s, v[5] * s, hi.z, lo.z);
+    split2h(v[6] * s, v[7] * s, hi.w, lo.w);
     unsigned char* p = img + (((long)c * R + sgn) * lpp + t) * 32;
     *reinterpret_cast<uint4*>(p) = hi;
     *reinterpret_cast<uint4*>(p + 16) = lo;
@@ -269,7 +250,7 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) fb[j] = (unsigned)(PS_A_BYTES + ((wn * 2 + j) * 32 + l31) * 128 + ((lk ^ ff) * 16));
 
-    const float sc_inv = (1.0f / ps_scale(g.amax_a[0])) * (1.0f / ps_scale(g.amax_b[0]));
+    const float sc_inv = (1.0f / f16_scale(g.amax_a[0])) * (1.0f / f16_scale(g.amax_b[0]));
 
     int tile_m, tile_n, m0, n0, split = 0, kt0 = 0, kend = g.K;
     // AF32 cut roles: row ar of the tile, k group ag (8 values), its pieces' slot XOR af; avoff = byte offset of its row (rows past M:
@@ -336,7 +317,7 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
                      : "=&v"(ra0), "=&v"(ra1) : "v"(vo), "s"(rsA) : "memory");
     };
     // ... and its fp16x3 cut (the rule of ps_pack_rows_kernel) into the stage of that k-tile
-    const float sc_a = AF32 ? ps_scale(g.amax_a[0]) : 1.0f;
+    const float sc_a = AF32 ? f16_scale(g.amax_a[0]) : 1.0f;
     auto cut_a = [&](int kt, int stage) {
         float v[8] = {ra0[0], ra0[1], ra0[2], ra0[3], ra1[0], ra1[1], ra1[2], ra1[3]};
         const int kb = (kt0 + kt) * PS_BK;
@@ -345,10 +326,10 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
             for (int j = 0; j < 8; ++j) v[j] = (kb + ag * 8 + j < kend) ? v[j] : 0.f;
         }
         uint4 hi, lo;
-        ps_split2(v[0] * sc_a, v[1] * sc_a, hi.x, lo.x);
-        ps_split2(v[2] * sc_a, v[3] * sc_a, hi.y, lo.y);
-        ps_split2(v[4] * sc_a, v[5] * sc_a, hi.z, lo.z);
-        ps_split2(v[6] * sc_a, v[7] * sc_a, hi.w, lo.w);
+        split2h(v[0] * sc_a, v[1] * sc_a, hi.x, lo.x);
+        split2h(v[2] * sc_a, v[3] * sc_a, hi.y, lo.y);
+        split2h(v[4] * sc_a, v[5] * sc_a, hi.z, lo.z);
+        split2h(v[6] * sc_a, v[7] * sc_a, hi.w, lo.w);
         unsigned char* const p = ps_smem + stage * PS_STAGE + ar * 128;
         *reinterpret_cast<uint4*>(p + ((ag ^ af) * 16)) = hi;
         *reinterpret_cast<uint4*>(p + (((4 + ag) ^ af) * 16)) = lo;

@@ -16,6 +16,7 @@
 // Algorithmic bytes per pass: L*E*4 per row (+ L*4 weights); x[b] is shared by the `tries` rows of an utterance
 // through L2.
 #include "common.h"
+#include "split.h"
 #include <stdlib.h>
 #include <type_traits>
 // Bit-exact parity with oracle/kmeans.py needs IEEE mul/add (no FMA contraction), sqrt and divide: contraction is
@@ -888,7 +889,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     float w_nxt = 1.0f;
     if constexpr (HAS_W) {
         const int r1 = row0 + tt;
-        wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L), (short)0, (int)(a.L * 4), 0x00020000);
+        wrs = make_rsrc(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L, (unsigned)(a.L * 4));
         w_nxt = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, (unsigned)((base + (long)kk * LANES + lane) * 4), 0, 0));
     }
     // sums role
@@ -903,7 +904,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     // staging: thread -> (point pr of a slab, 16-byte group c4) of BOTH slabs of an iteration
     const int pr = tid / V4, c4 = tid - pr * V4;
     // the utterance as a buffer resource: 32-bit offsets, and rows past L come back as zeros without a test (raw buffer bounds check)
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), (short)0, (int)(a.L * E_ * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(a.L * E_ * 4));
     float4 pf[2];
     unsigned foff = (unsigned)((base + pr) * E_ + c4 * 4) * 4u;   // byte offset of this thread's group in slab 0 of the column
     auto fetch = [&](int it) {
@@ -1121,11 +1122,11 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
     float w_nxt = 1.0f;
     if constexpr (HAS_W) {                                          // silence weights: the LABELS are weighted, the inertia distance is not
         const int r1 = row0 + tt;
-        wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L), (short)0, (int)(a.L * 4), 0x00020000);
+        wrs = make_rsrc(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L, (unsigned)(a.L * 4));
         w_nxt = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, (unsigned)((base + kk * 64 + lane) * 4), 0, 0));
     }
     const int pr = tid / V4, c4 = tid - pr * V4;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), (short)0, (int)(a.L * E_ * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(a.L * E_ * 4));
     float4 pf[2];
     const unsigned foff = (unsigned)((base + pr) * E_ + c4 * 4) * 4u;
     auto fetch = [&](int it) {

@@ -30,6 +30,7 @@
 // Every wait is bounded: on timeout an error word is set, every ring stops waiting, the (wrong) launch ends, and the host reads
 // the word (ams_blstm_ring_error).  Residency: n_chains * NW <= 512 workgroups of 256 threads (<= 2 per CU).
 #include "common.h"
+#include "split.h"
 #include <stdlib.h>
 
 // tuning aids (A/B builds through AMS_HIP_LIB): where the backward kernel requests the next step's operands
@@ -57,7 +58,6 @@
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int TB = 16;          // batch rows per chain
@@ -81,19 +81,9 @@ struct RingArgs {
     const float* amax_u;        // forward, fp16x3: device pointer to an upper bound of max |U| over both recurrent kernels
 };
 
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-// aux 16 = sc1: the load bypasses this CU's L1 and is served by the L2 (MI355X_MICROARCH.md, inter-workgroup visibility)
-__device__ __forceinline__ float4 ld16_l2(rsrc_t rs, unsigned byte_off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 16));
-}
-__device__ __forceinline__ float ld4_l2(rsrc_t rs, unsigned byte_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, byte_off, 0, 16));
-}
 __device__ __forceinline__ void st16(rsrc_t rs, float* base, unsigned byte_off, float4 v, bool fast) {
     if (fast) *reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off) = v;       // stays in this XCD's L2
-    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), rs, byte_off, 0, 16);   // write-through
+    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), rs, byte_off, 0, 16);   // write-through
 }
 
 // Gate non-linearities of the ring epilogue: ~1 ulp like libm's, without its branches and special-case paths (the epilogue is on
@@ -205,55 +195,6 @@ __device__ __forceinline__ bool chain_shares_l2(const RingArgs& a, int chain, in
 // ~17 cycles instead of 63 of 32 per wave and step.  U's slice lives in registers as three bf16 images (108 VGPRs instead of 63);
 // h_{t-1} is split on arrival: every lane already holds exactly the 8 k-slots per MFMA its A fragment needs, because an MFMA's k
 // order is free as long as A and B agree (slot e = 3 i + j of lane group q <-> k = 12 r_i + 3 q + j on both sides).
-typedef __bf16 rbf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 rbf16x2_t __attribute__((ext_vector_type(2)));
-typedef float rf32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned ring_pk_bf16(float a, float b) {
-    const rf32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, rbf16x2_t));
-}
-__device__ __forceinline__ void ring_split3(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
-    hi = ring_pk_bf16(a, b);
-    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
-    mid = ring_pk_bf16(ra, rb);
-    const float sa = ra - __uint_as_float(mid << 16), sb = rb - __uint_as_float(mid & 0xffff0000u);
-    lo = ring_pk_bf16(sa, sb);
-}
-
-typedef _Float16 rf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 rf16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 rf16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void ring_split2h(float a, float b, unsigned& hi, unsigned& mid) {
-    const rf32x2_t v = {a, b};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, rf16x2_t));
-    const rf16x2_t h = __builtin_bit_cast(rf16x2_t, hi);
-    const rf32x2_t r = {a - (float)h[0], b - (float)h[1]};
-    mid = __builtin_bit_cast(unsigned, __builtin_convertvector(r, rf16x2_t));
-}
-// One value as the two fp16 terms of ring_split2h in ONE dword, hi | mid << 16: what the PRODUCER of h_t publishes in the fp16x3 forward
-// ring (round 5).  A consumer then builds its MFMA operand planes with two v_perm_b32 per pair of k-slots; splitting on arrival was two
-// conversions back, two subtractions and two packed conversions per pair in each of the 25 consumers' four waves, on the hand-off cycle.
-__device__ __forceinline__ unsigned ring_pack_hm(float v) {
-    const _Float16 hi = (_Float16)v;
-    const _Float16 mid = (_Float16)(v - (float)hi);
-    return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, mid) << 16);
-}
-// 2^(13 - floor(log2(amax))); 1 for 0, denormals, Inf, NaN (csrc/gemm.hip::f16_scale)
-__device__ __forceinline__ float ring_f16_scale(float amax) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    if (e == 0 || e == 255) return 1.0f;
-    const int se = 127 + 13 - (e - 127);
-    return (se >= 1 && se <= 254) ? __uint_as_float((unsigned)se << 23) : 1.0f;
-}
-
-// the same scale and its exact inverse (both powers of two; (1, 1) where ring_f16_scale gives 1)
-__device__ __forceinline__ void ring_f16_scale2(float amax, float& sc, float& inv) {
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
-    const int se = 127 + 13 - (e - 127);
-    const bool ok = (e != 0 && e != 255 && se >= 1 && se <= 253);
-    sc = ok ? __uint_as_float((unsigned)se << 23) : 1.0f;
-    inv = ok ? __uint_as_float((unsigned)(254 - se) << 23) : 1.0f;
-}
 
 template <int NR, int ARITH = 0>      // 0: v_mfma_f32_16x16x4_f32, 1: bf16x6, 2: fp16x3 (a.amax_u = bound of the recurrent kernels)
 __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
@@ -292,11 +233,11 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
 
     // X6: the same weights as three bf16 images, 8 k-slots per lane and MFMA: slot e = 3 i + j, MFMA m = e / 8 (zero beyond 3 NR)
     constexpr int NM = (X6 || F16) ? (3 * NR + 7) / 8 : 1;
-    rbf16x8_t bq[NM][3][F16 ? 2 : 3];                              // [MFMA][column tile][plane hi / mid / lo]
+    bf16x8_t bq[NM][3][F16 ? 2 : 3];                               // [MFMA][column tile][plane hi / mid / lo]
     // fp16x3 (csrc/gemm.hip): U scaled by a power of two from its bound and split in two fp16 terms; h_{t-1} (|h| < 1) scaled by 2^13
     float sc_u = 1.0f, sc_inv = 1.0f;
     if constexpr (F16) {
-        sc_u = ring_f16_scale(a.amax_u[0]);
+        sc_u = f16_scale(a.amax_u[0]);
         sc_inv = (1.0f / sc_u) * (1.0f / 8192.0f);
 #pragma unroll
         for (int m = 0; m < NM; ++m)
@@ -307,11 +248,11 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                 for (int pr = 0; pr < 4; ++pr) {
                     const int e0 = 8 * m + 2 * pr, e1 = e0 + 1;
                     const float v0 = e0 < 3 * NR ? bw[e0 / 3][e0 % 3][t] : 0.f, v1 = e1 < 3 * NR ? bw[e1 / 3][e1 % 3][t] : 0.f;
-                    ring_split2h(v0 * sc_u, v1 * sc_u, hi[pr], mid[pr]);
+                    split2h(v0 * sc_u, v1 * sc_u, hi[pr], mid[pr]);
                 }
                 const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]};
-                bq[m][t][0] = __builtin_bit_cast(rbf16x8_t, h4);
-                bq[m][t][1] = __builtin_bit_cast(rbf16x8_t, m4);
+                bq[m][t][0] = __builtin_bit_cast(bf16x8_t, h4);
+                bq[m][t][1] = __builtin_bit_cast(bf16x8_t, m4);
             }
     }
     if constexpr (X6) {
@@ -324,12 +265,12 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                 for (int pr = 0; pr < 4; ++pr) {
                     const int e0 = 8 * m + 2 * pr, e1 = e0 + 1;
                     const float v0 = e0 < 3 * NR ? bw[e0 / 3][e0 % 3][t] : 0.f, v1 = e1 < 3 * NR ? bw[e1 / 3][e1 % 3][t] : 0.f;
-                    ring_split3(v0, v1, hi[pr], mid[pr], lo[pr]);
+                    split3(v0, v1, hi[pr], mid[pr], lo[pr]);
                 }
                 const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]}, l4 = {lo[0], lo[1], lo[2], lo[3]};
-                bq[m][t][0] = __builtin_bit_cast(rbf16x8_t, h4);
-                bq[m][t][1] = __builtin_bit_cast(rbf16x8_t, m4);
-                bq[m][t][2] = __builtin_bit_cast(rbf16x8_t, l4);
+                bq[m][t][0] = __builtin_bit_cast(bf16x8_t, h4);
+                bq[m][t][1] = __builtin_bit_cast(bf16x8_t, m4);
+                bq[m][t][2] = __builtin_bit_cast(bf16x8_t, l4);
             }
     }
 
@@ -391,7 +332,7 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
 #pragma unroll
                     for (int i = 0; i < NR; ++i) {
                         const int r = min(wave + 4 * i, NW - 1);
-                        hv[i] = ld16_l2(rs, rbase + (unsigned)(r * 4 + q) * 16u);
+                        hv[i] = ld16_sc1(rs, rbase + (unsigned)(r * 4 + q) * 16u);
                     }
                     __builtin_amdgcn_sched_barrier(0);          // all requests in flight before the first tag is looked at
                     bool ok = true;
@@ -419,13 +360,13 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
             if (s > 0) {
                 if constexpr (F16) {
                     f32x4 accs[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                    rf16x8_t aq[NM][2];
+                    f16x8_t aq[NM][2];
 #pragma unroll
                     for (int m = 0; m < NM; ++m) {
                         unsigned hi[4], mid[4];
 #pragma unroll
                         for (int pr = 0; pr < 4; ++pr) {
-                            // the granules carry hi | mid << 16 per value (ring_pack_hm at the producer): plane dwords by byte permutes
+                            // the granules carry hi | mid << 16 per value (pack_hm at the producer): plane dwords by byte permutes
                             const int e0 = 8 * m + 2 * pr, e1 = e0 + 1;
                             const unsigned p0 = e0 < 3 * NR ? __float_as_uint(e0 % 3 == 0 ? hv[e0 / 3].x : e0 % 3 == 1 ? hv[e0 / 3].y : hv[e0 / 3].z) : 0u;
                             const unsigned p1 = e1 < 3 * NR ? __float_as_uint(e1 % 3 == 0 ? hv[e1 / 3].x : e1 % 3 == 1 ? hv[e1 / 3].y : hv[e1 / 3].z) : 0u;
@@ -433,8 +374,8 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                             mid[pr] = __builtin_amdgcn_perm(p1, p0, 0x07060302u);
                         }
                         const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]};
-                        aq[m][0] = __builtin_bit_cast(rf16x8_t, h4);
-                        aq[m][1] = __builtin_bit_cast(rf16x8_t, m4);
+                        aq[m][0] = __builtin_bit_cast(f16x8_t, h4);
+                        aq[m][1] = __builtin_bit_cast(f16x8_t, m4);
                     }
                     constexpr int PA[3] = {1, 0, 0};                    // lo.hi, hi.lo | hi.hi: the cross terms in their own accumulator
                     constexpr int PB[3] = {0, 1, 0};
@@ -444,7 +385,7 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                         for (int m = 0; m < NM; ++m)
 #pragma unroll
                             for (int t3 = 0; t3 < 3; ++t3) {
-                                const rf16x8_t fb = __builtin_bit_cast(rf16x8_t, bq[m][t3][PB[pp]]);
+                                const f16x8_t fb = __builtin_bit_cast(f16x8_t, bq[m][t3][PB[pp]]);
                                 if (pp < 2) accs[t3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[m][PA[pp]], fb, accs[t3], 0, 0, 0);
                                 else acc[t3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[m][PA[pp]], fb, acc[t3], 0, 0, 0);
                             }
@@ -452,7 +393,7 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                     for (int t3 = 0; t3 < 3; ++t3) acc[t3] = (acc[t3] + accs[t3]) * sc_inv;
                 } else if constexpr (X6) {
                     f32x4 accs[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                    rbf16x8_t aq[NM][3];
+                    bf16x8_t aq[NM][3];
 #pragma unroll
                     for (int m = 0; m < NM; ++m) {
                         unsigned hi[4], mid[4], lo[4];
@@ -461,12 +402,12 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
                             const int e0 = 8 * m + 2 * pr, e1 = e0 + 1;
                             const float v0 = e0 < 3 * NR ? (e0 % 3 == 0 ? hv[e0 / 3].x : e0 % 3 == 1 ? hv[e0 / 3].y : hv[e0 / 3].z) : 0.f;
                             const float v1 = e1 < 3 * NR ? (e1 % 3 == 0 ? hv[e1 / 3].x : e1 % 3 == 1 ? hv[e1 / 3].y : hv[e1 / 3].z) : 0.f;
-                            ring_split3(v0, v1, hi[pr], mid[pr], lo[pr]);
+                            split3(v0, v1, hi[pr], mid[pr], lo[pr]);
                         }
                         const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]}, l4 = {lo[0], lo[1], lo[2], lo[3]};
-                        aq[m][0] = __builtin_bit_cast(rbf16x8_t, h4);
-                        aq[m][1] = __builtin_bit_cast(rbf16x8_t, m4);
-                        aq[m][2] = __builtin_bit_cast(rbf16x8_t, l4);
+                        aq[m][0] = __builtin_bit_cast(bf16x8_t, h4);
+                        aq[m][1] = __builtin_bit_cast(bf16x8_t, m4);
+                        aq[m][2] = __builtin_bit_cast(bf16x8_t, l4);
                     }
                     constexpr int PA[6] = {2, 0, 1, 1, 0, 0};           // lo.hi, hi.lo, mid.mid, mid.hi, hi.mid | hi.hi: smallest first
                     constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
@@ -520,8 +461,8 @@ __global__ __launch_bounds__(256) void lstm_ring_fwd_kernel(RingArgs a) {
         // hand h_s to the ring first: lanes ul = 0, 3, 6, 9 assemble {h[ul], h[ul+1], h[ul+2], tag}
         // h of the next two lanes of this 16-lane row: DPP row shifts on the VALU (the ds_bpermute form of __shfl_down goes through the LDS
         // crossbar: two more round trips on the hand-off's critical path)
-        // fp16x3: the published value is h * 2^13 already split (ring_pack_hm) -- one split per value instead of one per consumer wave
-        const int hb = F16 ? (int)ring_pack_hm(h * 8192.0f) : __float_as_int(h);
+        // fp16x3: the published value is h * 2^13 already split (pack_hm) -- one split per value instead of one per consumer wave
+        const int hb = F16 ? (int)pack_hm(h * 8192.0f) : __float_as_int(h);
         const float h0 = __int_as_float(hb);
         const float h1 = __int_as_float(__builtin_amdgcn_update_dpp(0, hb, 0x101, 0xf, 0xf, true));     // row_shl:1
         const float h2 = __int_as_float(__builtin_amdgcn_update_dpp(0, hb, 0x102, 0xf, 0xf, true));     // row_shl:2
@@ -628,12 +569,12 @@ __global__ __launch_bounds__(256) void lstm_ring_bwd_kernel(RingArgs a) {
     // U^T slice as B fragments: k = own gate column (gate * 12 + local unit), n = unit of the output tile
     const int n16 = lane & 15, q = lane >> 4;
     float bw[F16 ? 1 : NI][UW];
-    rf16x8_t wq[F16 ? NI : 1][2];                               // fp16x3: [tile][plane hi / mid], k-slots 0..7 of the lane group (K = 32 MFMA)
-    rf16x4_t wr[F16 ? NI : 1][2];                               //         ... k-slots 8..11 (K = 16 MFMA)
+    f16x8_t wq[F16 ? NI : 1][2];                                // fp16x3: [tile][plane hi / mid], k-slots 0..7 of the lane group (K = 32 MFMA)
+    f16x4_t wr[F16 ? NI : 1][2];                                //         ... k-slots 8..11 (K = 16 MFMA)
     float sc_u_inv = 1.0f;
     if constexpr (F16) {
         float sc_u;
-        ring_f16_scale2(a.amax_u[0], sc_u, sc_u_inv);
+        f16_scale2(a.amax_u[0], sc_u, sc_u_inv);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int tl = wave + 4 * i, unit_row = tl * 16 + n16;
@@ -646,14 +587,14 @@ __global__ __launch_bounds__(256) void lstm_ring_bwd_kernel(RingArgs a) {
                     const int e = 2 * pr + h, ucol = w * UW + e;            // k = 12 q + e: gate q, local unit e
                     v[h] = (tl < NT && unit_row < H && ucol < H) ? U[(long)unit_row * a.ldu + q * H + ucol] * sc_u : 0.f;
                 }
-                ring_split2h(v[0], v[1], hi[pr], mid[pr]);
+                split2h(v[0], v[1], hi[pr], mid[pr]);
             }
             const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]};
             const uint2 h2 = {hi[4], hi[5]}, m2 = {mid[4], mid[5]};
-            wq[i][0] = __builtin_bit_cast(rf16x8_t, h4);
-            wq[i][1] = __builtin_bit_cast(rf16x8_t, m4);
-            wr[i][0] = __builtin_bit_cast(rf16x4_t, h2);
-            wr[i][1] = __builtin_bit_cast(rf16x4_t, m2);
+            wq[i][0] = __builtin_bit_cast(f16x8_t, h4);
+            wq[i][1] = __builtin_bit_cast(f16x8_t, m4);
+            wr[i][0] = __builtin_bit_cast(f16x4_t, h2);
+            wr[i][1] = __builtin_bit_cast(f16x4_t, m2);
         }
     } else {
 #pragma unroll
@@ -736,7 +677,7 @@ __global__ __launch_bounds__(256) void lstm_ring_bwd_kernel(RingArgs a) {
 #endif
             for (;;) {                                          // every wave waits for the pieces it sums itself
 #pragma unroll
-                for (int k = 0; k < NPG; ++k) pv[k] = ld16_l2(rs, base + (unsigned)(min(pgc + PG * k, NW - 1) * tile_f) * 4u);
+                for (int k = 0; k < NPG; ++k) pv[k] = ld16_sc1(rs, base + (unsigned)(min(pgc + PG * k, NW - 1) * tile_f) * 4u);
                 __builtin_amdgcn_sched_barrier(0);              // all requests in flight before the first piece is looked at
                 bool ok = true;
 #pragma unroll
@@ -817,24 +758,24 @@ __global__ __launch_bounds__(256) void lstm_ring_bwd_kernel(RingArgs a) {
                 const auto s32 = __builtin_amdgcn_permlane32_swap(mu, mu, false, false);
                 mu = max(s32[0], s32[1]);
                 float sc, sc_inv;
-                ring_f16_scale2(__uint_as_float(mu), sc, sc_inv);
+                f16_scale2(__uint_as_float(mu), sc, sc_inv);
                 sc_inv *= sc_u_inv;
-                rf16x8_t bq[2];                                 // plane hi / mid, k-slots 0..7
-                rf16x4_t br[2];                                 //                 k-slots 8..11
+                f16x8_t bq[2];                                  // plane hi / mid, k-slots 0..7
+                f16x4_t br[2];                                  //                 k-slots 8..11
                 {
                     unsigned hi[6], mid[6];
-                    ring_split2h(v0.x * sc, v0.y * sc, hi[0], mid[0]);
-                    ring_split2h(v0.z * sc, v0.w * sc, hi[1], mid[1]);
-                    ring_split2h(v1.x * sc, v1.y * sc, hi[2], mid[2]);
-                    ring_split2h(v1.z * sc, v1.w * sc, hi[3], mid[3]);
-                    ring_split2h(v2.x * sc, v2.y * sc, hi[4], mid[4]);
-                    ring_split2h(v2.z * sc, v2.w * sc, hi[5], mid[5]);
+                    split2h(v0.x * sc, v0.y * sc, hi[0], mid[0]);
+                    split2h(v0.z * sc, v0.w * sc, hi[1], mid[1]);
+                    split2h(v1.x * sc, v1.y * sc, hi[2], mid[2]);
+                    split2h(v1.z * sc, v1.w * sc, hi[3], mid[3]);
+                    split2h(v2.x * sc, v2.y * sc, hi[4], mid[4]);
+                    split2h(v2.z * sc, v2.w * sc, hi[5], mid[5]);
                     const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, m4 = {mid[0], mid[1], mid[2], mid[3]};
                     const uint2 h2 = {hi[4], hi[5]}, m2 = {mid[4], mid[5]};
-                    bq[0] = __builtin_bit_cast(rf16x8_t, h4);
-                    bq[1] = __builtin_bit_cast(rf16x8_t, m4);
-                    br[0] = __builtin_bit_cast(rf16x4_t, h2);
-                    br[1] = __builtin_bit_cast(rf16x4_t, m2);
+                    bq[0] = __builtin_bit_cast(f16x8_t, h4);
+                    bq[1] = __builtin_bit_cast(f16x8_t, m4);
+                    br[0] = __builtin_bit_cast(f16x4_t, h2);
+                    br[1] = __builtin_bit_cast(f16x4_t, m2);
                 }
                 // ONE accumulator per tile (the workgroup must fit beside two residency-capped product workgroups of 160 registers:
                 // <= 192 in all; with the cross terms in accumulators of their own it needed 230, and a ring launched behind such a

@@ -202,8 +202,7 @@ class Network(object):
         restore_model() / anything that calls _weights_written() drops the derived tensors; code that writes `.data` of a variable
         behind the model's back must call _weights_written() itself (as it must for captured steps)."""
         for v in get_default_graph().variables.values():
-            K.drop_frozen_derivatives(v)
-            v._ams_frozen = True
+            K.set_frozen(v, True)
 
     def restore_last_checkpoint(self):
         self.restore_model(self._dir())
@@ -227,6 +226,8 @@ class Network(object):
         g = get_default_graph()
         for v in g.global_variables():
             v.requires_grad_(False)
+        for v in self.trainable_variables:             # (an earlier freeze_weights() / optimize(): the optimizer writes these from now on)
+            K.set_frozen(v, False)
         opt = FlatOptimizer(self.trainable_variables, self.my_opt, self.learning_rate, self.decay_epoch,
                             self.gradient_clip, self.dist)
         F.OVERLAP.enabled = (bool(self.args.get('overlap_weight_grads', True)) and torch.cuda.is_available()
@@ -240,8 +241,7 @@ class Network(object):
             trained = set(id(v) for v in self.trainable_variables)
             for v in g.variables.values():
                 if id(v) not in trained:
-                    K.drop_frozen_derivatives(v)
-                    v._ams_frozen = True
+                    K.set_frozen(v, True)
         self.optimizer = opt
         self.increment_epoch = opt.increment_epoch
         g.summaries['optimize/learning_rate'] = Node('learning_rate', lambda run: opt.learning_rate())

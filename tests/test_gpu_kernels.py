@@ -184,6 +184,34 @@ def test_blstm_layer(ops, monkeypatch, B, T, D, H, ring):
     assert ops.persist_errors() == 0                            # no bounded in-launch wait timed out
 
 
+def test_a_derived_weight_image_follows_its_second_owner(ops, monkeypatch):
+    """The pre-split image of a BLSTM layer's projection kernels is derived from BOTH direction kernels (ops.derived, owners (Kf, Kb)):
+    with only Kf frozen it is cut again in the next pass, so a write to Kb is seen -- as by a layer with nothing frozen."""
+    B, T, D, H = 2, 3, 8, 8
+    monkeypatch.setattr(ops, 'F16X3', True)
+    monkeypatch.setattr(ops, 'PRESPLIT', True)
+    monkeypatch.setattr(ops, 'PASS', [ops.PASS[0]])
+    rng = np.random.RandomState(B * T + H)
+    lim = np.sqrt(6.0 / (D + 5 * H))
+    x = rng.randn(B, T, D)
+    Kf, Kb = rng.uniform(-lim, lim, (D + H, 4 * H)) * 3, rng.uniform(-lim, lim, (D + H, 4 * H)) * 3
+    bf, bb = rng.randn(4 * H) * 0.1, rng.randn(4 * H) * 0.1
+    xd, Kfd, Kbd, bfd, bbd = dev(x), dev(Kf), dev(Kb), dev(bf), dev(bb)
+    ops.set_frozen(Kfd, True)
+    launches = ops.PS_LAUNCHES[0]
+    first = host(ops.blstm_fwd(xd, Kfd, bfd, Kbd, bbd)[0])
+    assert ops.PS_LAUNCHES[0] == launches + 1                   # the projection did run from pre-split images
+    ops.PASS[0] += 1
+    Kbd.mul_(1.5)
+    second = host(ops.blstm_fwd(xd, Kfd, bfd, Kbd, bbd)[0])
+    ops.PASS[0] += 1
+    plain = host(ops.blstm_fwd(xd, dev(Kf), bfd, dev(Kb * 1.5), bbd)[0])           # nothing frozen
+    print('second vs nothing frozen %.3e, second vs first %.3e' % (rel(second, plain), rel(second, first)))
+    assert rel(second, plain) < TOL
+    assert rel(second, first) > TOL
+    assert ops.persist_errors() == 0
+
+
 @pytest.mark.parametrize('ring', ['1', 'safe'])
 @pytest.mark.parametrize('B,T,D,H', [(5, 7, 12, 8), (20, 9, 24, 20), (3, 4, 16, 300), (33, 12, 8, 37), (4, 5, 6, 336), (64, 6, 40, 300),
                                        (6, 10, 600, 24), (18, 5, 16, 130), (7, 6, 16, 200), (9, 4, 16, 250)])

@@ -234,11 +234,11 @@ def test_inference_recipe_keeps_weight_derivatives_until_the_weights_are_written
             o1 = model.infer(feed, 0)[2].clone()
             o2 = model.infer(feed, 0)[2].clone()
             Kf = g.variables['prediction/forward_BLSTM_0/rnn/basic_lstm_cell/kernel']
-            assert ops._frozen(Kf) == frozen and hasattr(Kf, '_ams_wcat') == frozen
+            assert ops._frozen(Kf) == frozen and (ops.derived_entry(Kf, 'wcat') is not None) == frozen
             Kf.data.mul_(1.5)
             g.variables['prediction/W'].data.mul_(0.7)
             model._weights_written()
-            assert not hasattr(Kf, '_ams_wcat')
+            assert ops.derived_entry(Kf, 'wcat') is None
             o3 = model.infer(feed, 0)[2].clone()
         assert torch.equal(o1, o2)
         assert torch.isfinite(o3).all() and not torch.equal(o1, o3)
