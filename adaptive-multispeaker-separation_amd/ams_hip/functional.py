@@ -1043,14 +1043,23 @@ class KMeansSoft(Function):
         return (dX,) + (None,) * 10
 
 
+def _soft_kmeans_has_backward(E, C):
+    """A soft k-means under gradient runs ams_kmeans_soft_bwd in backward(): its table is narrower than the forward's (include/ams.h),
+    so a pair the backward refuses is refused HERE, before the forward launches anything -- not after a forward pass that succeeded."""
+    if ops.kmeans_in_domain(E, C) and not ops.kmeans_in_domain(E, C, soft_grad=True):
+        raise ops.AmsError('soft k-means under gradient at (E, C) = (%d, %d): the forward would run and backward() fail -- %s, %s'
+                           % (E, C, ops.KMEANS_TEXT, ops.KMEANS_SOFT_BWD_TEXT))
+
+
 def kmeans(X, init_idx, C, tries, iterations, beta, w, assign_at_end, normalize_input=True, faithful_tile=True, pre_norm=None):
     """KMeans.network (Kmeans_2.py:86-111).  Returns (centroids [b,C,E], labels, best_try).
     pre_norm: a callable returning u with X = l2-normalise(u) over E (same shape) -- a soft k-means under gradient that normalises its
     input takes u instead of X (see KMeansSoft, from_u); X may then be a callable too and is not evaluated."""
     if pre_norm is not None and beta is not None and normalize_input and torch.is_grad_enabled():
-        u = _c(pre_norm())
+        u = pre_norm()
         if u.requires_grad:
-            return KMeansSoft.apply(u, init_idx, C, tries, iterations, beta, w, assign_at_end, True, faithful_tile, True)
+            _soft_kmeans_has_backward(u.shape[-1], C)
+            return KMeansSoft.apply(_c(u), init_idx, C, tries, iterations, beta, w, assign_at_end, True, faithful_tile, True)
     if pre_norm is not None and normalize_input and callable(X) and (beta is None or not torch.is_grad_enabled()):
         # no gradient wanted: the Normalize layer and the k-means' own normalisation in ONE pass over u (the bits of the two passes);
         # the once-normalised tensor is not evaluated
@@ -1067,6 +1076,7 @@ def kmeans(X, init_idx, C, tries, iterations, beta, w, assign_at_end, normalize_
             xn = ops.kmeans_normalize(X) if normalize_input else X
             sel, out, best, _ = ops.kmeans_run(xn, init_idx, C, tries, iterations, beta, w, assign_at_end, faithful_tile)
         return sel, out, best
+    _soft_kmeans_has_backward(X.shape[-1], C)
     return KMeansSoft.apply(X, init_idx, C, tries, iterations, beta, w, assign_at_end, normalize_input, faithful_tile)
 
 

@@ -111,7 +111,12 @@ class KMeans(object):
 
     def __init__(self, nb_clusters, centroids_init=None, nb_tries=10, nb_iterations=10, input_tensor=None,
                  normalize_input=True, latent_space_tensor=None, beta=None, threshold=2.5, assign_at_end=True,
-                 init_indices=None, seeding='reference', pre_norm=None, dist=None):
+                 init_indices=None, seeding='reference', pre_norm=None, dist=None, embedding_size=None):
+        if embedding_size is not None:
+            # the width of the points, where the caller knows it at construction (separate_host.build_separate): a pair without a kernel
+            # is refused now (ops.KMEANS_PAIRS), not by the library at the first call
+            from . import ops
+            ops.check_kmeans_domain(embedding_size, nb_clusters)
         if seeding not in ('reference', 'fast', 'keyed'):
             raise ValueError("seeding must be 'reference', 'fast' or 'keyed', got %r" % (seeding,))
         # Data parallel: the host streams of 'reference' / 'fast' are consumed row by row, so with G ranks utterance j of EVERY shard

@@ -83,6 +83,9 @@ def build_adapt_cost(m):
     back, front = m.back, m.front
     x_mix, x_non_mix = m.x_mix, m.x_non_mix
     f1, f2 = m.conv_filter, m.conv_filter_2
+    if not m.pretraining and getattr(m, 'sepNet', None) is not None:
+        from . import separate_host
+        separate_host.require_soft_kmeans_backward(m.sepNet)       # front fine-tuning: this cost reads what `separate` gives
 
     # the pair table (one pass over the waveforms) is shared by the cost and by the SDR-improvement summary; the summary's own
     # arithmetic (gradient-free, for pit_cost_adapt two more cross-batch products) runs only in a step that fetches it

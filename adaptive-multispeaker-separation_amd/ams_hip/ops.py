@@ -42,6 +42,76 @@ def _chk_rows(*ts):
             raise AmsError('ams_hip ops need fp32 tensors with dense rows, got %s %s' % (t.dtype, tuple(t.stride())))
 
 
+# ------------------------------------------------------------------ (embedding size, speakers / clusters) domains of the instantiated kernels
+# The tables of include/ams.h, once on the host side: the library answers AMS_E_INVALID_ARG outside them, the models refuse such a pair
+# when they are constructed (check_*_domain below), and tests/test_gpu_dispatch_arms.py holds them against the header's own statement.
+KMEANS_PAIRS = frozenset([(E, C) for E in (40, 8) for C in (2, 3, 4, 5, 6)] + [(20, 2), (20, 3)])      # ams_kmeans_iterate / _assign, hard
+KMEANS_SOFT_FWD_PAIRS = KMEANS_PAIRS                                                                   # ... the same two calls with beta >= 0
+KMEANS_SOFT_BWD_PAIRS = frozenset([(40, C) for C in (2, 3, 4, 5, 6)] + [(8, 2), (8, 3), (8, 5), (8, 6), (20, 2)])     # ams_kmeans_soft_bwd
+LOSS_E = (3, 4, 8, 16, 20, 32, 40)                  # ams_l41_loss_* (all four), ams_danet_recon_*, ams_dpcl_loss_bwd
+L41_MAX_S = 6                                       # ams_l41_loss_*: 1 <= S <= 6
+DANET_MAX_S = 4                                     # ams_danet_recon_*: one float4 of masks per bin
+DPCL_MAX_S = 8                                      # ams_dpcl_loss_*: 1 <= S <= 8 ...
+DPCL_MAX_E_PLUS_S = 64                              # ... and E + S <= 64 (four 16-wide tiles of the augmented Gram)
+
+
+def _pairs_text(pairs):
+    by_e = {}
+    for E, C in sorted(pairs):
+        by_e.setdefault(E, []).append(C)
+    return ', '.join('(%d, %s)' % (E, '|'.join(str(c) for c in cs)) for E, cs in sorted(by_e.items(), reverse=True))
+
+
+KMEANS_TEXT = 'k-means (ams_kmeans_iterate / ams_kmeans_assign) takes (embedding_size, clusters) in ' + _pairs_text(KMEANS_PAIRS)
+KMEANS_SOFT_BWD_TEXT = 'its backward (ams_kmeans_soft_bwd) takes ' + _pairs_text(KMEANS_SOFT_BWD_PAIRS)
+
+
+def kmeans_in_domain(E, C, soft_grad=False):
+    return (int(E), int(C)) in (KMEANS_SOFT_BWD_PAIRS if soft_grad else KMEANS_PAIRS)
+
+
+def l41_in_domain(E, S):
+    return int(E) in LOSS_E and 1 <= int(S) <= L41_MAX_S
+
+
+def danet_in_domain(E, S):
+    return int(E) in LOSS_E and 1 <= int(S) <= DANET_MAX_S
+
+
+def dpcl_in_domain(E, S):
+    return int(E) >= 1 and 1 <= int(S) <= DPCL_MAX_S and int(E) + int(S) <= DPCL_MAX_E_PLUS_S
+
+
+def check_kmeans_domain(E, C, soft_grad=False):
+    """Refusal at construction (ValueError, as the seven-speaker one of models/network.py): a separator whose k-means has no kernel for
+    its (embedding_size, nb_speakers) would train to the end and fail at its first inference; soft_grad: a fine-tuning recipe, whose
+    soft k-means also runs backward, would fail in its first backward()."""
+    if not kmeans_in_domain(E, C):
+        raise ValueError('--embedding_size %d --nb_speakers %d: no k-means kernel for this pair -- %s; a model of this size can be '
+                         'trained but not separated with' % (E, C, KMEANS_TEXT))
+    if soft_grad and not kmeans_in_domain(E, C, True):
+        raise ValueError('--embedding_size %d --nb_speakers %d: the soft k-means of a fine-tuning recipe runs forward at this pair but '
+                         'has no backward kernel -- %s, %s' % (E, C, KMEANS_TEXT, KMEANS_SOFT_BWD_TEXT))
+
+
+def check_l41_domain(E, S):
+    if not l41_in_domain(E, S):
+        raise ValueError('--embedding_size %d --nb_speakers %d: the L41 loss kernels (ams_l41_loss_*) take embedding_size in %s and '
+                         '1 to %d speakers' % (E, S, ', '.join(str(e) for e in LOSS_E), L41_MAX_S))
+
+
+def check_danet_domain(E, S):
+    if not danet_in_domain(E, S):
+        raise ValueError('--embedding_size %d --nb_speakers %d: the DANet reconstruction kernels (ams_danet_recon_*) take embedding_size '
+                         'in %s and 1 to %d speakers' % (E, S, ', '.join(str(e) for e in LOSS_E), DANET_MAX_S))
+
+
+def check_dpcl_domain(E, S):
+    if not dpcl_in_domain(E, S):
+        raise ValueError('--embedding_size %d --nb_speakers %d: the deep-clustering loss kernels (ams_dpcl_loss_*) take 1 to %d speakers '
+                         'and embedding_size + nb_speakers <= %d' % (E, S, DPCL_MAX_S, DPCL_MAX_E_PLUS_S))
+
+
 def _twin(a, b):
     """True when a and b are the two halves of one row-interleaved block [R, 2, C] (optim.FlatOptimizer twin layout)."""
     if a is None or b is None or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:

@@ -3,6 +3,7 @@
 import torch
 
 from . import functional as F
+from . import ops
 from .graph import Node, get_default_graph
 
 
@@ -10,13 +11,15 @@ def build_separate(sep, KMeans):
     """Separator.separate (network.py:554-582): KMeans on the embeddings -> masks -> masked mixture representation."""
     pred, X_input = sep.prediction, sep.X_input
     E, S = sep.embedding_size, sep.S
+    ops.check_kmeans_domain(E, S)                              # at construction: not as AMS_E_INVALID_ARG at the first inference
     emb = Node('embeddings', lambda run: pred.value(run).reshape(pred.value(run).shape[0], -1, E))
     sep.embeddings = emb
     lat = Node('latent', lambda run: X_input.value(run).abs(), register=False) if sep.with_silence else None
     km = KMeans(nb_clusters=S, nb_tries=sep.nb_tries, nb_iterations=sep.nb_steps, input_tensor=emb, beta=sep.beta,
                 latent_space_tensor=lat, threshold=sep.threshold, assign_at_end=sep.args['end_assign'],
                 init_indices=sep.args.get('kmeans_init_indices'), seeding=sep.args.get('kmeans_seeding') or 'reference',
-                pre_norm=(sep._embed, E) if getattr(sep, '_embed_normalized', False) else None, dist=getattr(sep, 'dist', None))
+                pre_norm=(sep._embed, E) if getattr(sep, '_embed_normalized', False) else None, dist=getattr(sep, 'dist', None),
+                embedding_size=E)
     sep.kmeans = km
     _, labels = km.network
 
@@ -85,8 +88,17 @@ def build_enhance_cost(sep):
     return cost
 
 
+def require_soft_kmeans_backward(sep):
+    """Called where a cost is wired on top of `separate` (the fine-tuning recipes): a SOFT k-means then also runs backward, and
+    ams_kmeans_soft_bwd has fewer (E, C) pairs than the forward (include/ams.h) -- refused here, not in the first backward()."""
+    km = getattr(sep, 'kmeans', None)
+    if km is not None and km.beta is not None:
+        ops.check_kmeans_domain(sep.embedding_size, sep.S, soft_grad=True)
+
+
 def build_cost_finetuning(model, est_node):
     """cost_finetuning (adapt.py:404-431 / network.py:697-724): 0.5*sum_l, mean_s, min over permutations, mean_b."""
+    require_soft_kmeans_backward(getattr(model, 'sepNet', model))
     x_non_mix = model.x_non_mix
 
     def _cost(run):

@@ -3,6 +3,7 @@
 import numpy as np
 
 from ams_hip import functional as F
+from ams_hip import ops as ams_ops
 from ams_hip.graph import Node, get_default_graph, scope
 from models.network import Separator
 from utils.ops import BLSTM, Conv1D, f_props, _graph_rng
@@ -15,6 +16,7 @@ class L41Model(Separator):
         kwargs['mask_b'] = -1.0
 
         super(L41Model, self).__init__(graph, **kwargs)
+        ams_ops.check_l41_domain(self.embedding_size, self.S)
 
         if self.sampling is not None:
             # negative sampling (L41.py:69-147): limits of the loss kernel (csrc/l41.hip)

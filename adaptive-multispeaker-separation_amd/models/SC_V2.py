@@ -22,6 +22,7 @@ class L41ModelV2(Separator):
                              'kernels hold four masks per bin; the other separators take up to 6' % kwargs['nb_speakers'])
 
         super(L41ModelV2, self).__init__(graph, **kwargs)
+        K.check_danet_domain(self.embedding_size, self.S)       # the source-contrastive term's table (ops.check_l41_domain) contains it
 
         if self.loss_with_silence and self.add_dilated and not self.plugged:
             # SC_V2.py:51-56: the mask is taken from the X the prediction reads -- [B,T,4F] behind the dilated stack -- and multiplied

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """Deep Clustering separator (reference models/dpcl.py), host mirror over the HIP kernels."""
 from ams_hip import functional as F
+from ams_hip import ops as K
 from ams_hip.graph import Node, get_default_graph, scope
 from models.network import Separator
 from utils.ops import BLSTM, Conv1D, f_props
@@ -13,6 +14,7 @@ class DPCL(Separator):
         kwargs['mask_b'] = 0.0
 
         super(DPCL, self).__init__(graph, **kwargs)
+        K.check_dpcl_domain(self.embedding_size, self.S)        # the loss; `separate` adds the k-means' own, narrower table
         self.init_separator()
 
     @scope

@@ -505,7 +505,7 @@ ams_status ams_l41_loss_ns_bwd(const float* emb, const float* y, const float* vs
  *   attr[b,s,:] = sum_p v[b,p,:] m[b,p,s] / (1e-12 + sum_p m[b,p,s]);   a = sigmoid(<attr[b,s,:], v[b,p,:]>)
  *   cost[0] = mean_b mean_s mean_p (x_non_mix[b,p,s] - x_input[b,p] a[b,p,s])^2
  * v [B,TF,E] the embeddings as the network emits them (NOT normalised), y [B,TF,S], x_sil / x_input [B,TF], x_non_mix [B,S,TF]
- * (xnm_rows != 0: the rows the front / the STFT writes) or [B,TF,S] (xnm_rows = 0).  Same (E, S) domain as ams_l41_loss_fwd.
+ * (xnm_rows != 0: the rows the front / the STFT writes) or [B,TF,S] (xnm_rows = 0).  E as ams_l41_loss_fwd, 1 <= S <= 4 (one float4 of masks per bin).
  * Forward: two reads of v.  g [B,TF,S] and dattr [B,S,E] (both or neither; NULL = cost only) receive what the backward needs:
  * g = d cost / d logit and dattr = (sum_p g v) / (1e-12 + sum_p m).  Backward: dv = upstream[0] * sum_s (g attr + m dattr) -- no read
  * of v; accumulate != 0 ADDS it to what dv holds (the gradient ams_l41_loss_bwd wrote: one read-modify-write, no temporary);

@@ -63,7 +63,11 @@ CASES = [(T, Fq, E, S, kind) for (T, Fq) in ((3, 50), (9, 257)) for (E, S) in ((
 
 @pytest.mark.parametrize('T,Fq,E,S,kind', CASES)
 def test_reconstruction_cost_and_gradient(F, T, Fq, E, S, kind):
-    B = 2
+    reconstruction_case(F, 2, T, Fq, E, S, kind)
+
+
+def reconstruction_case(F, B, T, Fq, E, S, kind):
+    """The body of test_reconstruction_cost_and_gradient (B = 2 there); other batch and embedding sizes: tests/test_gpu_dispatch_arms.py."""
     V, y, X, X_nm = _inputs(100 * E + 10 * S + T, B, T, Fq, E, S, kind)
     m = R.soft_masks(y)
     if kind == 'empty_speaker':

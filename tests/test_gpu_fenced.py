@@ -26,6 +26,7 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 from oracle import optim as ooptim
+from tests import test_gpu_dispatch_arms as arms
 from tests.fenced import Fence
 
 E_ = 'test_gpu_edge_cases'
@@ -39,6 +40,15 @@ MS = 'test_gpu_many_speakers_kernels'
 PS = 'test_gpu_gemm_ps'
 DX = 'test_gpu_gemm_ps_dx'
 BB = 'test_gpu_bss_batch'
+DP = 'test_gpu_dispatch_arms'
+
+
+def _arm(cases, *head):
+    """The row of a case table of tests/test_gpu_dispatch_arms.py that starts with `head` (its seed comes with it)."""
+    found = [c for c in cases if tuple(c[:len(head)]) == head]
+    assert len(found) == 1, (head, found)
+    return tuple(found[0])
+
 
 DANET_SMALLEST = [(3, 50, 8, 2, 'binary'), (3, 50, 8, 2, 'fractional')]          # tests/test_gpu_danet.py: CASES[0], CASES[1]
 
@@ -117,6 +127,14 @@ ROWS = [
     # inputs not fenced; their float64 workspaces come from torch.empty in utils/bss_eval.py: fenced by the patch alone
     (BB, 'test_edge_tiles', (37,)),
     (BB, 'test_potrf_depends_on_its_matrix_only', (100,)),
+    # the arms whose vector width, row pitch or ownership differ from E = 40's (tests/test_gpu_dispatch_arms.py): five and two float4 per
+    # point in the k-means passes, one and four per point in the L41 loss, four Gram tiles and the 4-byte staging of an odd E in the
+    # deep-clustering loss
+    (DP, 'test_hard_kmeans', _arm(arms.HARD_CASES, 20, 3, 8449, 3, True)), (DP, 'test_hard_kmeans', _arm(arms.HARD_CASES, 8, 4, 8449, 3, True)),
+    (DP, 'test_soft_kmeans_forward', _arm(arms.SOFT_FORWARD_CASES, 20, 3, 8449)),
+    (DP, 'test_soft_kmeans_forward', _arm(arms.SOFT_FORWARD_CASES, 8, 4, 197)),
+    (DP, 'test_l41_loss', (4, 4, True, True)), (DP, 'test_l41_loss', (16, 6, False, False)),
+    (DP, 'test_dpcl_from_the_network_output', (60, 4, 2561)), (DP, 'test_dpcl_from_the_network_output', (45, 5, 77)),
 ]
 
 # (module, test function, arguments, base, outcome)
@@ -136,6 +154,8 @@ ODD_ROWS = [
     (K1, 'test_blstm_layer', (5, 7, 12, 8, '1'), 4, 'passes'),
     (K1, 'test_blstm_layer', (5, 7, 12, 8, '0'), 4, 'passes'),
     (K1, 'test_optimizers', (), 4, 'passes'),
+    (DP, 'test_hard_kmeans', _arm(arms.HARD_CASES, 20, 3, 8449, 3, True), 4, 'passes'),
+    (DP, 'test_l41_loss', (4, 4, True, True), 4, 'passes'),
 ]
 
 
@@ -170,7 +190,7 @@ def host(t):
 # backward or of the five-tries kernels is therefore not seen by these rows (the hard and soft k-means FORWARD kernels read fenced
 # inputs in the test_gpu_kernels2.py rows).  test_gpu_many_speakers_kernels.py::test_soft_kmeans_backward calls
 # test_gpu_kmeans_soft.py's test and is 'not fenced' in the same way.
-UPLOADS = {E_: 'dev', K1: 'dev', K2: 'dev', DA: 'dev', PS: 'dev', DX: 'dev', MS: 'dev',
+UPLOADS = {E_: 'dev', K1: 'dev', K2: 'dev', DA: 'dev', PS: 'dev', DX: 'dev', MS: 'dev', DP: 'dev',
            DC: 'not fenced', KS: 'not fenced', KT: 'not fenced', BB: 'not fenced'}
 INPUTS_NOT_FENCED = [(DC, 'test_layer'), (KS, 'test_soft_kmeans_backward'), (KT, 'test_five_tries_per_read_is_bit_exact'),
                      (MS, 'test_soft_kmeans_backward'), (BB, 'test_edge_tiles'), (BB, 'test_potrf_depends_on_its_matrix_only')]

@@ -247,9 +247,9 @@ def test_backward_ring_as_fp16x3_one_scale_per_row(ops, monkeypatch, B, T, D, H,
     ops.raise_on_ring_errors()
 
 
-@pytest.mark.parametrize('B,TF,E,S', [(2, 300, 8, 2), (3, 5000, 40, 2), (2, 2049, 40, 3), (2, 77, 3, 2), (1, 700, 20, 4),
-                                        (2, 2561, 40, 8)])
-def test_l2norm_dpcl(ops, B, TF, E, S):
+def l2norm_dpcl_forward_case(ops, B, TF, E, S):
+    """The first part of test_l2norm_dpcl: l2-normalise and the loss forward on the normalised embeddings (ams_dpcl_loss_fwd), which has
+    no list of E of its own (E + S <= 64) -- tests/test_gpu_dispatch_arms.py runs it past the E of the backward's switch too."""
     rng = np.random.RandomState(TF)
     u = rng.randn(B, TF * E)
     u[0, :E] = 0.0                                           # exercises the eps clamp
@@ -265,6 +265,13 @@ def test_l2norm_dpcl(ops, B, TF, E, S):
     assert abs(o[0] - c_ref) < TOL * max(1.0, abs(c_ref))
     for k in range(3):
         assert abs(o[1 + k] - terms[k]) < TOL * max(1.0, abs(terms[k]))
+    return u, V_ref, inv_ref, V, inv, Y, c_ref, terms, Vd, Yd, ws
+
+
+@pytest.mark.parametrize('B,TF,E,S', [(2, 300, 8, 2), (3, 5000, 40, 2), (2, 2049, 40, 3), (2, 77, 3, 2), (1, 700, 20, 4),
+                                        (2, 2561, 40, 8)])
+def test_l2norm_dpcl(ops, B, TF, E, S):
+    u, V_ref, inv_ref, V, inv, Y, c_ref, terms, Vd, Yd, ws = l2norm_dpcl_forward_case(ops, B, TF, E, S)
     dV_ref = odpcl.dpcl_cost_bwd(V_ref.reshape(B, TF, E), Y)
     dV = ops.dpcl_loss_bwd(Vd, Yd, ws)
     assert rel(host(dV), dV_ref) < 5 * TOL

@@ -265,17 +265,27 @@ def test_kmeans_hard_bit_exact(F, ops, b, L, E, C, tries, with_w, end):
     assert np.array_equal(lab.cpu().numpy(), lab_ref)
 
 
-def test_kmeans_soft_forward(F):
-    rng = np.random.RandomState(9)
-    b, L, E, C, tries = 2, 3000, 40, 2, 2
+def kmeans_soft_forward_inputs(seed, b, L, E, C, tries):
+    rng = np.random.RandomState(seed)
     centers = rng.randn(C, E) * 2.0
     X = centers[rng.randint(0, C, (b, L))] + rng.randn(b, L, E) * 0.7
     w = (rng.rand(b, L) > 0.2).astype(np.float64)
     idx = np.stack([rng.choice(L, C, replace=False) for _ in range(b * tries)]).astype(np.int32)
+    return X, w, idx
+
+
+def kmeans_soft_forward_case(F, seed, b, L, E, C, tries, upload=None):
+    """The body of test_kmeans_soft_forward at other sizes (tests/test_gpu_dispatch_arms.py); upload: the caller's dev (a fenced one)."""
+    up = upload or dev
+    X, w, idx = kmeans_soft_forward_inputs(seed, b, L, E, C, tries)
     cent_ref, lab_ref, best_ref = okm.kmeans(X, idx, C, tries, 5, beta=10.0, notsilent=w, assign_at_end=True)
-    cent, lab, best = F.kmeans(dev(X), dev(idx, np.int32), C, tries, 5, 10.0, dev(w), True)
+    cent, lab, best = F.kmeans(up(X), up(idx, np.int32), C, tries, 5, 10.0, up(w), True)
     assert np.array_equal(best.cpu().numpy(), best_ref)
     assert rel(host(cent), cent_ref) < 1e-4 and np.abs(host(lab) - lab_ref).max() < 1e-3
+
+
+def test_kmeans_soft_forward(F):
+    kmeans_soft_forward_case(F, 9, 2, 3000, 40, 2, 2, upload=dev)
 
 
 @pytest.mark.parametrize('Bt,L,W,N,P,hop,S', [(4, 512, 64, 16, 128, 128, 2), (6, 1024, 128, 40, 256, 128, 2), (2, 300, 32, 5, 40, 24, 1),

@@ -45,16 +45,26 @@ def torch_soft_kmeans(X, idx, C, tries, iters, beta, w, end, faithful=True):
 @pytest.mark.parametrize('b,L,E,C,tries,iters,with_w,end', [(2, 3000, 40, 2, 2, 3, True, True), (2, 2500, 8, 3, 1, 4, True, False),
                                                               (1, 4200, 40, 2, 1, 2, False, True), (8, 20480, 40, 2, 1, 3, True, True)])
 def test_soft_kmeans_backward(b, L, E, C, tries, iters, with_w, end, monkeypatch):
-    from ams_hip import functional as F, ops
-    tagged = []
-    real_tag = ops.tag_amax
-    monkeypatch.setattr(ops, 'tag_amax', lambda t, a: (tagged.append((t, a)), real_tag(t, a))[1])
-    rng = np.random.RandomState(L + C)
+    soft_kmeans_backward_case(L + C, b, L, E, C, tries, iters, with_w, end, monkeypatch)
+
+
+def soft_kmeans_backward_inputs(seed, b, L, E, C, tries, with_w):
+    rng = np.random.RandomState(seed)
     centers = rng.randn(C, E) * 1.5
     X = centers[rng.randint(0, C, (b, L))] + rng.randn(b, L, E) * 0.8
     w = (rng.rand(b, L) > 0.2).astype(np.float64) if with_w else None
     idx = np.stack([rng.choice(L, C, replace=False) for _ in range(b * tries)])
     R1, R2 = rng.randn(b, L, C), rng.randn(b, C, E)
+    return X, w, idx, R1, R2
+
+
+def soft_kmeans_backward_case(seed, b, L, E, C, tries, iters, with_w, end, monkeypatch):
+    """The body of test_soft_kmeans_backward (which draws from seed L + C); other seeds and sizes: tests/test_gpu_dispatch_arms.py."""
+    from ams_hip import functional as F, ops
+    tagged = []
+    real_tag = ops.tag_amax
+    monkeypatch.setattr(ops, 'tag_amax', lambda t, a: (tagged.append((t, a)), real_tag(t, a))[1])
+    X, w, idx, R1, R2 = soft_kmeans_backward_inputs(seed, b, L, E, C, tries, with_w)
     beta = 3.0
     Xt = torch.from_numpy(X).requires_grad_()
     sel_r, out_r, best_r = torch_soft_kmeans(Xt, torch.from_numpy(idx), C, tries, iters, beta, None if w is None else torch.from_numpy(w), end)

@@ -165,9 +165,16 @@ def _l41_case(S, rng, B=3, T=4, Fq=70, E=40, NS=23):
 @pytest.mark.parametrize('normalize', [True, False])
 @pytest.mark.parametrize('S', [5, 6])
 def test_l41_loss(F, S, normalize, from_u):
-    rng = np.random.RandomState(6 + S)
-    B, T, Fq, E = 3, 4, 70, 40                                      # 280 bins per utterance: two blocks, the second of 24
-    spk, I, y = _l41_case(S, rng)
+    l41_loss_case(F, 6 + S, 40, S, normalize, from_u)
+
+
+def l41_loss_case(F, seed, E, S, normalize, from_u, upload=None):
+    """The body of test_l41_loss (E = 40, seed 6 + S there); the other embedding sizes: tests/test_gpu_dispatch_arms.py.  upload: the
+    caller's dev (a fenced one)."""
+    dev = upload or globals()['dev']
+    rng = np.random.RandomState(seed)
+    B, T, Fq = 3, 4, 70                                             # 280 bins per utterance: two blocks, the second of 24
+    spk, I, y = _l41_case(S, rng, E=E)
     if from_u:
         u = rng.randn(B, T, Fq * E) * np.exp(rng.randn(B, T, 1))
         u[0, 0, :E] = 0.0                                           # the epsilon clamp
@@ -188,10 +195,16 @@ def test_l41_loss(F, S, normalize, from_u):
 @pytest.mark.parametrize('from_u', [False, True])
 @pytest.mark.parametrize('method,K', [('k-nearest', 6), ('random', 16)])
 def test_l41_loss_negative_sampling_five_speakers(F, method, K, from_u):
-    S, rate, normalize = 5, 0.3, True
-    rng = np.random.RandomState(60 + K)
-    B, T, Fq, E, NS = 3, 4, 70, 40, 23
-    spk, I, y = _l41_case(S, rng)
+    l41_negative_sampling_case(F, 60 + K, 40, 5, method, K, from_u)
+
+
+def l41_negative_sampling_case(F, seed, E, S, method, K, from_u, upload=None):
+    """The body of test_l41_loss_negative_sampling_five_speakers (E = 40, S = 5, seed 60 + K there)."""
+    dev = upload or globals()['dev']
+    rate, normalize = 0.3, True
+    rng = np.random.RandomState(seed)
+    B, T, Fq, NS = 3, 4, 70, 23
+    spk, I, y = _l41_case(S, rng, E=E)
     if from_u:
         u = rng.randn(B, T, Fq * E) * np.exp(rng.randn(B, T, 1))
         emb, inv = odense.l2norm_fwd(u, E)
@@ -221,9 +234,18 @@ def test_l41_loss_negative_sampling_five_speakers(F, method, K, from_u):
 @pytest.mark.parametrize('S', [5, 6])
 def test_dpcl_loss(F, S, E):
     """models/dpcl.py's entry (the network output before Normalize, fused normalise + loss) on the generic path of S > 4."""
+    dpcl_loss_u_case(F, S, E, 9, 33)                                 # 297 points
+
+
+def dpcl_loss_u_case(F, S, E, T, Fq, zero_row=False, upload=None):
+    """The body of test_dpcl_loss at T * Fq points; zero_row: one point of u all zeros (the eps clamp, as test_gpu_kernels.py::
+    test_l2norm_dpcl has it); upload: the caller's dev (a fenced one).  Other sizes: tests/test_gpu_dispatch_arms.py."""
+    dev = upload or globals()['dev']
     rng = np.random.RandomState(10 * S + E)
-    B, T, Fq = 2, 9, 33                                              # 297 points
+    B = 2
     u = rng.randn(B, T, Fq * E) * np.exp(rng.randn(B, T, 1))
+    if zero_row:
+        u[0, 0, :E] = 0.0
     lab = rng.randint(0, S, (B, T * Fq))
     lab[0, :100] = 0                                                 # unbalanced classes
     Y = np.eye(S)[lab]
@@ -242,13 +264,7 @@ def test_dpcl_loss(F, S, E):
     assert rel(host(ut.grad), du_ref) < 5 * TOL
 
 
-@pytest.mark.parametrize('b,L,E,C,tries,with_w,end,seed,best_expected',
-                         [(2, 8449, 40, 5, 2, False, True, 13453, [1, 0]), (2, 4100, 40, 6, 3, True, False, 10109, [2, 0]),
-                          (2, 2500, 8, 5, 1, 'real', True, 7500, [0, 0]), (1, 8449, 40, 6, 2, 'mixed', True, 14449, [1])])
-def test_kmeans_hard_bit_exact(F, ops, b, L, E, C, tries, with_w, end, seed, best_expected):
-    """The body of test_gpu_kernels2.py::test_kmeans_hard_bit_exact (same order of random draws) for five and six clusters.  L = 8449 is
-    one full 8192-point chunk plus a second of one slab and one point.  The seeds are ones for which the oracle uses every cluster
-    (others meet the reference's empty-cluster NaN)."""
+def kmeans_hard_inputs(seed, b, L, E, C, tries, with_w):
     rng = np.random.RandomState(seed)
     centers = rng.randn(C, E).astype(np.float32) * 2.0
     lab_true = rng.randint(0, C, (b, L))
@@ -259,6 +275,23 @@ def test_kmeans_hard_bit_exact(F, ops, b, L, E, C, tries, with_w, end, seed, bes
     elif with_w == 'mixed':
         w[:, ::3] = rng.uniform(0.05, 1.7, (b, L))[:, ::3].astype(np.float32)
     idx = np.stack([rng.choice(L, C, replace=False) for _ in range(b * tries)]).astype(np.int32)
+    return X, w, idx
+
+
+@pytest.mark.parametrize('b,L,E,C,tries,with_w,end,seed,best_expected',
+                         [(2, 8449, 40, 5, 2, False, True, 13453, [1, 0]), (2, 4100, 40, 6, 3, True, False, 10109, [2, 0]),
+                          (2, 2500, 8, 5, 1, 'real', True, 7500, [0, 0]), (1, 8449, 40, 6, 2, 'mixed', True, 14449, [1])])
+def test_kmeans_hard_bit_exact(F, ops, b, L, E, C, tries, with_w, end, seed, best_expected):
+    """The body of test_gpu_kernels2.py::test_kmeans_hard_bit_exact (same order of random draws) for five and six clusters.  L = 8449 is
+    one full 8192-point chunk plus a second of one slab and one point.  The seeds are ones for which the oracle uses every cluster
+    (others meet the reference's empty-cluster NaN)."""
+    kmeans_hard_case(F, ops, b, L, E, C, tries, with_w, end, seed, best_expected)
+
+
+def kmeans_hard_case(F, ops, b, L, E, C, tries, with_w, end, seed, best_expected, upload=None):
+    """The body of test_kmeans_hard_bit_exact; upload: the caller's dev (a fenced one).  Other (E, C): tests/test_gpu_dispatch_arms.py."""
+    dev = upload or globals()['dev']
+    X, w, idx = kmeans_hard_inputs(seed, b, L, E, C, tries, with_w)
     cent_ref, lab_ref, best_ref = okm.kmeans(X, idx, C, tries, 4, beta=None, notsilent=w, assign_at_end=end)
     assert np.isfinite(cent_ref).all()
     assert list(best_ref) == best_expected
