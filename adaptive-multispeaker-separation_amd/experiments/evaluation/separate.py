@@ -1,11 +1,16 @@
 # coding: utf-8
 """python -m experiments.evaluation.separate --model_folder ... --sortofmodel {STFT,front}[_enhanced]_{DPCL,L41}
-       --input mix.wav --output_prefix out [--hop H]
+       --input mix.wav --output_prefix out [--hop H] [--resample [--output_rate R] [--input_rate R]]
 
 Separate one whole recording: the model's inference recipe (the same ones experiments/evaluation/eval.py uses) on overlapping chunks
 of --chunk_size samples, the chunk outputs tracked across the chunk borders and cross-faded on the GPU (Network.separate_recording,
 ams_hip/stitch.py).  Input: 16-bit PCM mono .wav at config.fs, or .npy float32 [N].  Output: <prefix>_<k>.wav (or .npy for an .npy
-input), k = 0 .. nb_speakers - 1.  There is no resampling and no channel mixing: anything else is refused."""
+input), k = 0 .. nb_speakers - 1.  Without --resample there is no resampling and no channel mixing: anything else is refused.
+
+With --resample the input may be a 16-bit PCM .wav of 1 .. 8 channels at any rate whose reduced ratio to config.fs has both terms in
+1 .. 1024 (every standard rate from 11025 to 96000 Hz), or an .npy float32 [N] at --input_rate.  The frames are uploaded as they are;
+decoding, the channel down-mix and the way to config.fs are one GPU kernel, the separated tracks go back to --output_rate (default: the
+rate of the input) on the GPU as well (ams_hip/resample.py).  The outputs are mono."""
 import wave
 
 import numpy as np
@@ -18,11 +23,18 @@ def build_parser():
     p = MyArgs()
     p.parser.add_argument('--model_folder', help='Path to the Model folder to load', required=True)
     p.parser.add_argument('--sortofmodel', help='Sort of model', required=True)
-    p.parser.add_argument('--input', help='Recording to separate: 16-bit PCM mono .wav at %d Hz, or .npy float32 [N]' % config.fs,
+    p.parser.add_argument('--input', help='Recording to separate: 16-bit PCM mono .wav at %d Hz, or .npy float32 [N]; with --resample a '
+                          '16-bit PCM .wav of 1 .. 8 channels at any common rate, or .npy float32 [N] at --input_rate' % config.fs,
                           required=True)
     p.parser.add_argument('--output_prefix', help='Outputs are written to <prefix>_<k>.wav (.npy for an .npy input)', required=True)
     p.parser.add_argument('--hop', type=int, help='Samples between two chunks, ceil(chunk_size / 2) .. chunk_size - 1 '
                           '(default: half a chunk)', required=False, default=None)
+    p.parser.add_argument('--resample', action='store_true', help='Accept another sample rate and several channels: mix down, resample '
+                          'to %d Hz, separate, and resample the outputs back, all on the GPU' % config.fs)
+    p.parser.add_argument('--output_rate', type=int, help='Sample rate of the outputs with --resample (default: the rate of the input)',
+                          required=False, default=None)
+    p.parser.add_argument('--input_rate', type=int, help='Sample rate of an .npy input (required with --resample and .npy)',
+                          required=False, default=None)
     p.add_adapt_args()
     p.add_separator_args()
     return p
@@ -41,6 +53,18 @@ def read_wav(path, fs=None):
                              % (path, w.getframerate(), fs))
         raw = w.readframes(w.getnframes())
     return np.frombuffer(raw, dtype='<i2').astype(np.float32) / np.float32(32768.0)
+
+
+def read_recording(path):
+    """16-bit PCM of 1 .. 8 channels at any rate -> (int16 frames [N, CH], rate): the samples as the file has them, no arithmetic."""
+    with wave.open(path, 'rb') as w:
+        if w.getsampwidth() != 2 or w.getcomptype() != 'NONE':
+            raise SystemExit('%s is not 16-bit PCM (%d bytes per sample, compression %s)' % (path, w.getsampwidth(), w.getcomptype()))
+        if not 1 <= w.getnchannels() <= 8:
+            raise SystemExit('%s has %d channels: 1 .. 8 channels can be mixed down' % (path, w.getnchannels()))
+        channels, fs = w.getnchannels(), w.getframerate()
+        raw = w.readframes(w.getnframes())
+    return np.frombuffer(raw, dtype='<i2').reshape(-1, channels), fs
 
 
 def write_wav(path, x, fs=None):
@@ -65,14 +89,14 @@ def read_input(path):
     return read_wav(path)
 
 
-def write_outputs(prefix, out, as_npy):
+def write_outputs(prefix, out, as_npy, fs=None):
     paths = []
     for k, row in enumerate(np.asarray(out)):
         path = '%s_%d.%s' % (prefix, k, 'npy' if as_npy else 'wav')
         if as_npy:
             np.save(path, np.asarray(row, np.float32))
         else:
-            write_wav(path, row)
+            write_wav(path, row, fs)
         paths.append(path)
     return paths
 
@@ -82,7 +106,27 @@ def main(argv=None):
     if 'pretraining' in args.sortofmodel:
         raise SystemExit('--sortofmodel %s: a pretraining model separates with masks made from the clean sources; a recording comes '
                          'without them' % args.sortofmodel)
-    x = read_input(args.input)
+    fs = out_fs = None
+    if args.resample:
+        from ams_hip import resample
+        if args.input.endswith('.npy'):
+            if args.input_rate is None:
+                raise SystemExit('--resample with an .npy input needs --input_rate: an array carries no sample rate')
+            x, fs = read_input(args.input), args.input_rate
+        else:
+            x, fs = read_recording(args.input)
+            if args.input_rate not in (None, fs):
+                raise SystemExit('--input_rate %d, but %s has a sample rate of %d Hz' % (args.input_rate, args.input, fs))
+        out_fs = fs if args.output_rate is None else args.output_rate
+        try:
+            resample.ratio(fs, config.fs)
+            resample.ratio(config.fs, out_fs)
+        except ValueError as e:
+            raise SystemExit('%s: %s' % (args.input, e))
+    else:
+        if args.output_rate is not None or args.input_rate is not None:
+            raise SystemExit('--output_rate and --input_rate go with --resample')
+        x = read_input(args.input)
     if x.shape[0] < 1:
         raise SystemExit('%s is empty' % args.input)
     from experiments.evaluation.eval import pick
@@ -90,8 +134,8 @@ def main(argv=None):
     tr = inferencer(sep, 'inference', **vars(args))
     model = tr.prepare_inference()
     with tr.graph.as_default():
-        out = model.separate_recording(x, hop=args.hop).cpu().numpy()
-    paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'))
+        out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs).cpu().numpy()
+    paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'), out_fs)
     print('\n'.join(paths))
     return paths
 

@@ -614,14 +614,24 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
-    def separate_recording(self, x, hop=None, batch_size=None):
+    def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None):
         """x [N] (a tensor or anything numpy takes) -> out [S, N] on the device: chunks of the model's chunk_size, `hop` apart (default
-        half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h)."""
+        half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h).
+
+        fs: the sample rate of x (default config.fs, the rate the models work at).  At another rate -- or for int16 frames [N, CH], which
+        are decoded and mixed down -- x is brought to config.fs on the device (ams_hip.resample, include/ams_resample.h), separated as
+        above, and the [S, M] result is resampled to output_fs (default fs) and cut to ceil(N output_fs / fs) samples: N at the rate of
+        the input.  Nothing goes through the host between the upload and the result."""
         from ams_hip import stitch as St
         self._refuse_unless_separating()
         L = int(self.args['chunk_size'])
         H = St.default_hop(L) if hop is None else int(hop)
         St.check_geometry(L, H)
+        fs_in = config.fs if fs is None else int(fs)
+        fs_out = fs_in if output_fs is None else int(output_fs)
+        pcm = (x.dtype == torch.int16) if torch.is_tensor(x) else (getattr(x, 'dtype', None) == np.int16)
+        if pcm or fs_in != config.fs or fs_out != config.fs:
+            return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out)
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
@@ -629,6 +639,27 @@ class Network(object):
             raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
         est = self.infer_chunks(St.chunks(x, L, H), batch_size)
         return St.stitch(est, x.shape[0], H)[0]
+
+    def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out):
+        from ams_hip import resample as Rs
+        Rs.ratio(fs_in, config.fs)                                 # a ValueError before anything is uploaded
+        Rs.ratio(config.fs, fs_out)
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.array(x, dtype=np.int16 if pcm else np.float32))      # (a copy: frames read from a file are read-only)
+        x = x.to(device=get_default_graph().device, dtype=torch.int16 if pcm else torch.float32).contiguous()
+        if pcm and x.dim() == 1:
+            x = x.reshape(-1, 1)
+        if x.dim() != (2 if pcm else 1) or x.shape[0] < 1:
+            raise ValueError('separate_recording: float32 [N] or int16 frames [N, CH] of at least one sample, got %s %s'
+                             % (x.dtype, tuple(x.shape)))
+        N = x.shape[0]
+        x = Rs.from_pcm16(x, fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs)
+        out = self.separate_recording(x, hop=H, batch_size=batch_size)
+        if fs_out == config.fs:
+            return out
+        out = Rs.resample(out, config.fs, fs_out)
+        n_out = -((-N * fs_out) // fs_in)                          # <= out.shape[1]: the way back yields ceil(M fs_out / config.fs)
+        return out[:, :n_out].contiguous() if n_out < out.shape[1] else out
 
     def improvement(self, feed_dict, step):
         return self._eval_guarded(feed_dict, lambda run: [self.x_mix.value(run), self.x_non_mix.value(run), self.sdr_imp.value(run)])
