@@ -661,6 +661,74 @@ class Network(object):
         n_out = -((-N * fs_out) // fs_in)                          # <= out.shape[1]: the way back yields ceil(M fs_out / config.fs)
         return out[:, :n_out].contiguous() if n_out < out.shape[1] else out
 
+    def separate_recordings(self, xs, hop=None, batch_size=None, fs=None, output_fs=None):
+        """xs: a list of recordings, float32 [N_r] each (tensors or anything numpy takes) -> a list of [S, N_r] device tensors.  The chunks
+        of ALL recordings go through infer_chunks as one stream -- ceil(Ctot / batch_size) model passes instead of one or more per
+        recording -- and are cut, tracked and cross-faded by kernels whose launch count does not depend on len(xs)
+        (ams_hip.stitch_batch, include/ams_stitch_batch.h).  The results are views of one packed buffer.
+
+        A chunk's k-means seeds depend on the row of the batch it sits in (kmeans_init_indices has a row per batch row and try), and here
+        a chunk's row is its place in the stream: separate_recordings(xs)[r] is DEFINED as the stitch of the batched inference.  It is not
+        bit-equal to separate_recording(xs[r]) -- except for a single recording, where the rows coincide.
+
+        fs / output_fs as in separate_recording, for float32 [N_r] or int16 frames [N_r, CH] (all of one dtype): every recording goes
+        through the resampler on its own on the way in and out; the separation between is the batched one."""
+        from ams_hip import stitch as St
+        from ams_hip import stitch_batch as Sb
+        self._refuse_unless_separating()
+        if isinstance(xs, (torch.Tensor, np.ndarray)) or not hasattr(xs, '__len__'):
+            raise ValueError('separate_recordings: a list of recordings, got %s (one recording: separate_recording)' % type(xs).__name__)
+        xs = list(xs)
+        if not xs:
+            raise ValueError('separate_recordings: an empty list of recordings')
+        L = int(self.args['chunk_size'])
+        H = St.default_hop(L) if hop is None else int(hop)
+        St.check_geometry(L, H)
+        fs_in = config.fs if fs is None else int(fs)
+        fs_out = fs_in if output_fs is None else int(output_fs)
+        xs = [x if torch.is_tensor(x) else np.asarray(x) for x in xs]
+        kinds = set(str(x.dtype).replace('torch.', '') for x in xs)
+        if len(kinds) > 1:
+            raise ValueError('separate_recordings: recordings of one dtype, got %s' % sorted(kinds))
+        if kinds - {'int16', 'float32'}:
+            raise ValueError('separate_recordings: float32 [N] or int16 frames [N, CH], got %s' % sorted(kinds))
+        pcm = kinds == {'int16'}
+        for x in xs:
+            if x.ndim not in ((1, 2) if pcm else (1,)) or x.shape[0] < 1:
+                raise ValueError('separate_recordings: float32 [N] or int16 frames [N, CH] of at least one sample, got %s %s'
+                                 % (x.dtype, tuple(x.shape)))
+        device = get_default_graph().device
+        resampled = pcm or fs_in != config.fs or fs_out != config.fs
+        if resampled:
+            from ams_hip import resample as Rs
+            Rs.ratio(fs_in, config.fs)                             # a ValueError before anything is uploaded
+            Rs.ratio(config.fs, fs_out)
+            lengths, ys = [x.shape[0] for x in xs], []
+            for x in xs:
+                if not torch.is_tensor(x):
+                    x = torch.from_numpy(np.array(x))              # (a copy: frames read from a file are read-only)
+                x = x.to(device).contiguous()
+                ys.append(Rs.from_pcm16(x.reshape(x.shape[0], -1), fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs))
+            xs = ys
+        if all(torch.is_tensor(x) and x.is_cuda for x in xs):
+            mix, lay = Sb.chunks_many([x.contiguous() for x in xs], L, H, self.S)
+        else:
+            # recordings on the host: packed there and uploaded once
+            lay = Sb.layout([x.shape[0] for x in xs], L, H, self.S)
+            host = np.zeros(lay.x_total, np.float32)
+            for x, o, n in zip(xs, lay.x_off, lay.n):
+                host[o:o + n] = x.detach().cpu().numpy() if torch.is_tensor(x) else x
+            mix = Sb.chunks_packed(torch.from_numpy(host).to(device), lay)
+        outs = [o for o, _, _ in Sb.stitch_many(self.infer_chunks(mix, batch_size), lay)]
+        if not resampled or fs_out == config.fs:
+            return outs
+        res = []
+        for out, N in zip(outs, lengths):
+            out = Rs.resample(out.contiguous(), config.fs, fs_out)
+            n_out = -((-N * fs_out) // fs_in)                      # the rule of _separate_resampled
+            res.append(out[:, :n_out].contiguous() if n_out < out.shape[1] else out)
+        return res
+
     def improvement(self, feed_dict, step):
         return self._eval_guarded(feed_dict, lambda run: [self.x_mix.value(run), self.x_non_mix.value(run), self.sdr_imp.value(run)])
 
