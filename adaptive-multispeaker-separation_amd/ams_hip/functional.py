@@ -195,6 +195,11 @@ class BLSTMLayer(Function):
                 am_dx = (az, ctx.amax[1])
                 am_w = (ctx.amax[0], ops.amax_one(G.device), az)
             dx = ops.blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=am_dx) if need_dx else None
+            if not need_dx and ops.WGRAD_GROUP >= 1:
+                # first layer: no recurrence follows and nothing runs beside it -- the three products as ONE grouped launch on this
+                # stream (ops.blstm_bwd_weights_grouped; where it does not apply, the separate launches one after the other)
+                ops.blstm_bwd_weights(x, out, G, Kf.grad, bf.grad, Kb.grad, bb.grad, True, part='all', dbpart=dbpart, amax=am_w)
+                return None, None, None, None, None, None
             s = OVERLAP.fork(x, out, G, *([dbpart] if dbpart is not None else []))
             if not need_dx:
                 # first layer: no recurrence follows -- both streams work on the weight gradients, uncapped

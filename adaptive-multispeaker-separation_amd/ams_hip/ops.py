@@ -159,6 +159,12 @@ class _Profile(object):
         e.record(torch.cuda.current_stream())
         self.records.append((start, e, flops, nbytes, tag, label))
 
+    def also(self, tag='', label=''):
+        """A further product that the launch just recorded carries (a grouped launch): a record of its own, so that the list of tags
+        still names every product of a step, with no time and no work -- both are booked on the launch's first record."""
+        e = self.records[-1][1]
+        self.records.append((e, e, 0.0, 0.0, tag, label))
+
     def tags(self):
         return sorted(set(r[4] for r in self.records))
 
@@ -1257,6 +1263,47 @@ def blstm_bwd_dx(G, Kf, Kb, B, T, D, amax=None):
     return dx
 
 
+# the three weight-gradient products of a BLSTM layer as one grouped launch (include/ams.h: ams_blstm_bwd_weights_f32): 0 = the separate
+# launches, 1 = the first layer (functional.BLSTMLayer.backward: nothing runs beside it, uncapped).  Read once.
+WGRAD_GROUP = int(_os.environ.get('AMS_WGRAD_GROUP', '1'))
+
+
+def blstm_bwd_weights_grouped(x, out, G, dKf, dbf, dKb, dbb, accumulate, amax=None):
+    """part='all' of blstm_bwd_weights through ONE product launch and one finishing launch.  Returns False, having launched nothing,
+    where the grouped form does not apply: gradient blocks that are not twin-interleaved, widths that are no multiples of 4, bases off
+    a 16-byte boundary, the native-f32 arithmetic or a running range audit (the separate launches measure the operands under their keys)."""
+    B, T, D = x.shape
+    H = dKf.shape[1] // 4
+    M = B * T
+    lib = load()
+    key_wx, key_u = ('at_b_colsum', D, 8 * H, M), ('batched', H, 4 * H, M - 1, 2, True, False)
+    if not (x.is_cuda and M >= 2 and D % 4 == 0 and H % 4 == 0 and _twin(dKf, dKb) and _twin(dbf, dbb) and dKf.shape[0] == D + H
+            and x.is_contiguous() and out.is_contiguous() and G.is_contiguous() and not NOVEC and lib.ams_gemm_get_arith() != 0
+            and not F16_AUDIT.active and not any(t.data_ptr() % 16 for t in (x, out, G, dKf, dbf))):
+        return False
+    f16 = (F16X3 and amax is not None and all(a is not None for a in amax)
+           and key_wx not in F16_AUDIT.denied and key_u not in F16_AUDIT.denied)     # one class denied: bf16x6, which needs no range, for all
+    pad = LDS_PAD[0]
+    nb = lib.ams_blstm_bwd_weights_workspace_bytes(B, T, D, H, pad)
+    ws = _ws(nb, x)
+    ev = PROFILE.begin() if PROFILE.enabled else None
+    if f16:
+        cur = torch.cuda.current_stream()
+        for a in amax:
+            a.record_stream(cur)
+        pa = [_p(a) for a in amax]
+    else:
+        pa = [_vp(0)] * 3
+    check(lib.ams_blstm_bwd_weights_f32(B, T, D, H, _p(x), D, _p(out), _p(G), _p(dKf), 8 * H, _p(dbf), int(bool(accumulate)),
+                                        pa[0], pa[1], pa[2], pad, _p(ws), ws.numel() * 4, _s()), 'ams_blstm_bwd_weights_f32')
+    if ev is not None:
+        PROFILE.end(ev, 2.0 * M * D * 8 * H + 2 * 2.0 * (M - 1) * H * 4 * H,
+                    4.0 * (M * D + M * 8 * H + D * 8 * H) + 2 * 4.0 * ((M - 1) * H + (M - 1) * 4 * H + H * 4 * H),
+                    ('gemm16' if f16 else 'gemm') + '<1,0>', 'blstm_wgrad_group')
+        PROFILE.also(('gemm16' if f16 else 'gemm') + '<1,0>', 'blstm_wgrad_group.u')     # dWx + column sums above, the dU pair here
+    return True
+
+
 def blstm_bwd_weights(x, out, G, dKf, dbf, dKb, dbb, accumulate, part='all', dbpart=None, amax=None):
     """Weight gradients of one BLSTM layer from dZ (= G after blstm_bwd_recurrent), written (or accumulated) into the given
     buffers: dWx = x^T dZ, dU = h_prev^T dZ (time-shifted, masked at sequence boundaries), db = column sums.
@@ -1273,6 +1320,8 @@ def blstm_bwd_weights(x, out, G, dKf, dbf, dKb, dbb, accumulate, part='all', dbp
     dZb = G.view(-1)[4 * H:]
     acc = bool(accumulate)
     _chk_rows(dKf, dKb)
+    if part == 'all' and WGRAD_GROUP >= 1 and blstm_bwd_weights_grouped(x, out, G, dKf, dbf, dKb, dbb, acc, amax=amax):
+        return
     Dp = (D + 3) // 4 * 4
     if part in ('all', 'wx'):
         if Dp != D and x.is_cuda:

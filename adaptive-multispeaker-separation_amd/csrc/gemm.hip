@@ -208,6 +208,44 @@ __device__ __forceinline__ void locate_tile(GemmArgs& g, int& split, int& tile_m
     tile_m = band * GROUP_M + (within - tile_n * band_rows);
 }
 
+// GROUPED launch (ams_blstm_bwd_weights_f32): up to three products of one operand layout, tile configuration and arithmetic share ONE
+// launch.  The work items are numbered region by region, each region (split, tile) in its own band order; what differs between the
+// regions is listed here and replaces those fields of the launch's GemmArgs per item (all workgroup-uniform: scalar registers).
+struct GroupRegion {
+    const float* A; const float* B; float* C; const float* amax_a;
+    float* partial; float* bsum_part; float* bsum_out;
+    long lda;
+    int M, N, K, mask_period, mask_skip, group_m, splits, k_per_split;
+    int items;                 // tiles * splits
+};
+struct GroupTable { GroupRegion r[3]; int n_items; };
+// Work item `item` of a grouped launch: XCD x receives the x-th contiguous run of the flat order, as in locate_tile
+__device__ __forceinline__ void locate_group(GemmArgs& g, const GroupTable& t, int item, int& split, int& tile_m, int& tile_n, int bm, int bn) {
+    const int items = t.n_items;
+    const int q = items / 8, r = items % 8, xcd = item % 8, idx = item / 8;
+    item = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int i0 = t.r[0].items, i1 = i0 + t.r[1].items;
+    const int reg = item < i0 ? 0 : item < i1 ? 1 : 2;
+    item -= reg == 0 ? 0 : reg == 1 ? i0 : i1;
+    const GroupRegion& e = t.r[reg];            // (one indexed read of the kernel arguments per item: the three entries held in
+                                                // scalar registers at once left the persistent variant none to spare)
+    g.A = e.A; g.B = e.B; g.C = e.C; g.amax_a = e.amax_a;
+    g.partial = e.partial; g.bsum_part = e.bsum_part; g.bsum_out = e.bsum_out;
+    g.lda = e.lda;
+    g.M = e.M; g.N = e.N; g.K = e.K;
+    g.mask_period = e.mask_period; g.mask_skip = e.mask_skip;
+    g.group_m = e.group_m; g.splits = e.splits; g.k_per_split = e.k_per_split;
+    const int tiles_m = (g.M + bm - 1) / bm, tiles_n = (g.N + bn - 1) / bn;
+    const int ntiles = tiles_m * tiles_n;
+    split = item / ntiles;
+    const int bid = item - split * ntiles;
+    const int GROUP_M = g.group_m > 0 ? g.group_m : 1;
+    const int band = bid / (GROUP_M * tiles_n), within = bid - band * (GROUP_M * tiles_n);
+    const int band_rows = min(GROUP_M, tiles_m - band * GROUP_M);
+    tile_n = within / band_rows;
+    tile_m = band * GROUP_M + (within - tile_n * band_rows);
+}
+
 // Position `pos` of the flat (batch, split, tile) order -> tile; the second half of locate_tile for callers that enumerate positions
 // themselves (stream-K).  XCD x owns the positions [xcd_start(x), xcd_start(x) + xcd_len(x)).
 __device__ __forceinline__ int xcd_len(int items, int x) { return items / 8 + (x < items % 8 ? 1 : 0); }
@@ -694,14 +732,15 @@ __device__ long long g_x6_stamp[1024 * 8 * 8];
 #define X6_STAMP(ph) do { } while (0)
 #endif
 
-template <int AMODE, int BMODE, int CFG, int EPI, bool SEP, bool F16>
+template <int AMODE, int BMODE, int CFG, int EPI, bool SEP, bool F16, bool GRP = false>
 // PERSISTENT over work items (round 3): the grid is at most one resident set of workgroups (ams_gemm launch: 256 CUs x the
 // configuration's workgroups per CU) and a workgroup walks items blockIdx.x, + gridDim.x, ... .  The operands of the NEXT item's first
 // k-tile are requested BEFORE the epilogue stores of the finished one, so the stores (210 MB for the dense forward product: ~10 us per
 // round of 256 tiles with every workgroup storing at once, and nothing else resident on the CU to hide them) drain under the next
 // item's main loop instead of in front of the next workgroup's launch.  gridDim.x is a multiple of 8 (or the whole item count), so
 // an item stays on the XCD the flat order meant it for.
-__device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const smem) {
+// GRP: a grouped launch -- item -> (region, split, tile) through `tab` (locate_group), which replaces the region's fields of g0 per item.
+__device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const smem, const GroupTable* const tab = nullptr) {
     GemmArgs g = g0;
     using C = X6Cfg<CFG>;
     constexpr int BK = X6_BK, BMX = C::BMX, BNX = C::BNX, TM = C::TM, TN = C::TN;
@@ -726,7 +765,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
     // finished one: the capped single-accumulator ones are sized to sit beside a recurrence ring and that costs them
     // 20-40 VGPRs (next item's staging registers live over the epilogue); they fetch it after their stores.
     constexpr bool PERSIST = SEP && EPI == EPI_STORE;
-    const int n_items = (int)((long)((g0.M + BMX - 1) / BMX) * ((g0.N + BNX - 1) / BNX) * g0.splits * (g0.nbatch > 1 ? g0.nbatch : 1));
+    const int n_items = GRP ? tab->n_items
+                            : (int)((long)((g0.M + BMX - 1) / BMX) * ((g0.N + BNX - 1) / BNX) * g0.splits * (g0.nbatch > 1 ? g0.nbatch : 1));
     int split, tile_m, tile_n, m0, n0, k_begin, k_end, nk;
 
     // ---- the work list of this workgroup.  Plain launches: items blockIdx.x, + gridDim.x, ... (one item when not PERSIST).
@@ -793,7 +833,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
     auto setup = [&](int i) {
         g = g0;
         if (i < dp_count) {
-            locate_tile(g, split, tile_m, tile_n, BMX, BNX, (int)blockIdx.x + i * G);
+            if constexpr (GRP) locate_group(g, *tab, (int)blockIdx.x + i * G, split, tile_m, tile_n, BMX, BNX);
+            else locate_tile(g, split, tile_m, tile_n, BMX, BNX, (int)blockIdx.x + i * G);
             role = W_FULL;
             k_begin = split * g.k_per_split;
             k_end = min(g.K, k_begin + g.k_per_split);
@@ -1048,6 +1089,10 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
     for (; n_work > 0;) {                           // one work item per trip; every branch below is workgroup-uniform
         lane_consts();
         X6_STAMP(0);
+        if constexpr (GRP && F16) {                 // the regions' A operands have bounds of their own
+            sc_a = f16_scale(g.amax_a[0]);
+            sc_inv = (1.0f / sc_a) * (1.0f / sc_b);
+        }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1163,6 +1208,8 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
         const long ldo = g.splits > 1 ? g.N : g.ldc;
         const float* const ebias = g.bias;
         const int em0 = m0, en0 = n0;
+        int eM = 0, eN = 0, esplits = 0;            // a grouped launch: shape and slab count of the item's region (else g0's, read where they are used)
+        if constexpr (GRP) { eM = g.M; eN = g.N; esplits = g.splits; }
         if (PERSIST && more) {
             __syncthreads();                            // every wave has read its last fragments: the staging registers and LDS are free
             setup(wi + 1);
@@ -1199,9 +1246,9 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                 if (!(PERSIST && more)) __syncthreads();    // every wave has read its last fragments (the PERSIST path has just met for that)
                 const int rr = lane >> 4, c4 = (lane & 15) * 4;
                 const int col = en0 + wn * 64 + c4;
-                const bool cok = col < g0.N;                // (N % 4 == 0: a float4 is inside or outside)
+                const bool cok = col < (GRP ? eN : g0.N);                // (N % 4 == 0: a float4 is inside or outside)
                 float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (g0.splits == 1 && ebias && cok) bv = *reinterpret_cast<const float4*>(ebias + col);
+                if ((GRP ? esplits : g0.splits) == 1 && ebias && cok) bv = *reinterpret_cast<const float4*>(ebias + col);
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -1215,10 +1262,10 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
                         const int rl = p8 * 4 + rr;
                         float4 v = *reinterpret_cast<const float4*>(wl + rl * 64 + c4);
                         const int row = em0 + (wm * TM + i) * 32 + rl;
-                        if (row < g0.M && cok) {
+                        if (row < (GRP ? eM : g0.M) && cok) {
                             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
                             float4* const p = reinterpret_cast<float4*>(out + (long)row * ldo + col);
-                            if (g0.splits == 1 && g0.accumulate) { const float4 o = *p; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+                            if ((GRP ? esplits : g0.splits) == 1 && g0.accumulate) { const float4 o = *p; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
                             if (g0.relu) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
                             if (g0.emask) {
                                 const float4 e = *reinterpret_cast<const float4*>(g0.emask + (long)row * ldo + col);
@@ -1236,16 +1283,16 @@ __device__ __forceinline__ void x6_body(const GemmArgs& g0, unsigned char* const
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int col = en0 + (wn * TN + j) * 32 + l31;
-                    if (col >= g0.N) continue;
+                    if (col >= (GRP ? eN : g0.N)) continue;
                     if constexpr (F16) acc[i][j] *= sc_inv;
-                    const float bv = (g0.splits == 1 && ebias) ? ebias[col] : 0.f;
+                    const float bv = ((GRP ? esplits : g0.splits) == 1 && ebias) ? ebias[col] : 0.f;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int row = em0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                        if (row < g0.M) {
+                        if (row < (GRP ? eM : g0.M)) {
                             float v = acc[i][j][r] + bv;
                             float* p = out + (long)row * ldo + col;
-                            if (g0.splits == 1 && g0.accumulate) v += *p;
+                            if ((GRP ? esplits : g0.splits) == 1 && g0.accumulate) v += *p;
                             if (g0.relu) v = v > 0.f ? v : 0.f;
                             if (g0.emask) v = g0.emask[(long)row * ldo + col] > 0.f ? v : 0.f;
                             *p = v;
@@ -1314,6 +1361,14 @@ __global__ __launch_bounds__(X6Cfg<CFG>::WMC * X6Cfg<CFG>::WNC * 64, CFG == 0 ? 
     x6_body<AMODE, BMODE, CFG, EPI, SEP, F16>(g, smem);
 }
 
+// The grouped form of gemm_x6_kernel<A_COL, B_ROW, 3, EPI_STORE, SEP, F16>: the same body, its items taken from the region table.
+// SEP = true: uncapped, persistent walk over the items; false: residency-capped, one item per workgroup.
+template <bool SEP, bool F16>
+__global__ __launch_bounds__(X6Cfg<3>::WMC * X6Cfg<3>::WNC * 64, 1) void gemm_x6_group_kernel(const GemmArgs g, const GroupTable t) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[x6_lds(3)];
+    x6_body<A_COL, B_ROW, 3, EPI_STORE, SEP, F16, true>(g, smem, &t);
+}
+
 __global__ void splitk_reduce_kernel(const float* __restrict__ partial, float* __restrict__ C, const float* __restrict__ bias,
                                      int M, int N, long ldc, int splits, int accumulate, long c_zs, long bias_zs) {
     const long total = (long)M * N;
@@ -1368,6 +1423,46 @@ __global__ void bsum_finish_kernel(const float* __restrict__ part, float* __rest
     out[n] = accumulate ? out[n] + s : s;
 }
 
+// Finishing launch of a grouped product: blockIdx.y = 0 .. 2 adds the slabs of that region (splitk_reduce_vec_kernel's order: slabs
+// 0 .. s-1, then the old value; a region that stored directly has splits 1 and nothing to do), blockIdx.y = 3 finishes the column-sum
+// partials (bsum_finish_kernel's order).
+struct GroupFinish {
+    const float* partial[3]; float* C[3];
+    int M[3], N[3], splits[3];
+    long ldc; int accumulate;
+    const float* bsum_part; float* bsum_out; int bsum_n, bsum_splits;      // bsum_splits 0: the product launch finished them itself
+};
+__global__ __launch_bounds__(256) void group_finish_kernel(const GroupFinish f) {
+    const int y = blockIdx.y;
+    if (y == 3) {
+        const int n = blockIdx.x * 256 + threadIdx.x;
+        if (f.bsum_splits <= 0 || n >= f.bsum_n) return;
+        float s = 0.f;
+        for (int k = 0; k < f.bsum_splits; ++k) s += f.bsum_part[(long)k * f.bsum_n + n];
+        f.bsum_out[n] = f.accumulate ? f.bsum_out[n] + s : s;
+        return;
+    }
+    const int splits = y == 0 ? f.splits[0] : y == 1 ? f.splits[1] : f.splits[2];
+    if (splits <= 1) return;
+    const float* const partial = y == 0 ? f.partial[0] : y == 1 ? f.partial[1] : f.partial[2];
+    float* const C = y == 0 ? f.C[0] : y == 1 ? f.C[1] : f.C[2];
+    const int M = y == 0 ? f.M[0] : y == 1 ? f.M[1] : f.M[2], N = y == 0 ? f.N[0] : y == 1 ? f.N[1] : f.N[2];
+    const int n4 = N >> 2, total4 = M * n4;
+    const long total = (long)M * N;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total4; i += gridDim.x * 256) {        // splitk_reduce_vec_kernel's loop, no bias
+        const int m = i / n4, c4 = i - m * n4;
+        const float4* src = reinterpret_cast<const float4*>(partial) + i;
+        float4 s = src[0];
+        for (int k = 1; k < splits; ++k) {
+            const float4 v = src[(long)k * (total >> 2)];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        float4* p = reinterpret_cast<float4*>(C + (long)m * f.ldc) + c4;
+        if (f.accumulate) { const float4 o = *p; s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w; }
+        *p = s;
+    }
+}
+
 // Split-K factor from a small cost model calibrated on MI355X (scratch sweep, round 1):
 //   t(s) = n * (k_iters * 1.02us + 5us) / occ(n)  +  (s+1)*M*N*4 B / 2.5 TB/s        [s > 1]
 // n = ceil(tiles*s/256) workgroups end up on the busiest CU (equal-work workgroups time-share a CU's four
@@ -1389,8 +1484,9 @@ inline int x6_choose_cfg(int M, int N) {
 inline TilePlan x6_plan(int cfg) {
     return {x6_bm(cfg), x6_bn(cfg), X6_BK, cfg == 0 ? AMS_GEMM_X6_US16 : AMS_GEMM_X6_US16_2, cfg != 0 && AMS_X6_OCC1};
 }
-inline int choose_splits(int M, int N, int K, int nbatch, const TilePlan& tp, double* t_out = nullptr, int smax = 32) {
-    const int tiles = ceil_div(M, tp.bm) * ceil_div(N, tp.bn) * nbatch;
+// (the model itself, on `tiles` output tiles of `elems` output elements in all: one product, a batch, or the regions of a grouped
+// launch, which take one slab count for all of them)
+inline int choose_splits_tiles(int tiles, double elems, int K, const TilePlan& tp, double* t_out = nullptr, int smax = 32) {
     int best = 1;
     double best_t = 1e30;
     for (int s = 1; s <= smax; ++s) {
@@ -1401,11 +1497,14 @@ inline int choose_splits(int M, int N, int K, int nbatch, const TilePlan& tp, do
         // an 8-wave configuration is alone on its CU whatever the grid: no discount for few workgroups per CU
         const double occ = tp.alone ? 1.0 : n <= 1 ? 0.62 : (n == 2 ? 0.80 : (n == 3 ? 0.92 : 1.0));
         double t = n * ((kps / 16.0) * tp.us16 + 5.0) / occ;
-        if (s2 > 1) t += (double)(s2 + 1) * M * N * nbatch * 4.0 / 2.5e6;
+        if (s2 > 1) t += (double)(s2 + 1) * elems * 4.0 / 2.5e6;        // (whole numbers below 2^53: the same value in any order)
         if (t < best_t - 1e-9) { best_t = t; best = s2; }
     }
     if (t_out) *t_out = best_t;
     return best;
+}
+inline int choose_splits(int M, int N, int K, int nbatch, const TilePlan& tp, double* t_out = nullptr, int smax = 32) {
+    return choose_splits_tiles(ceil_div(M, tp.bm) * ceil_div(N, tp.bn) * nbatch, (double)M * N * nbatch, K, tp, t_out, smax);
 }
 // what a workspace query assumes: the process-wide arithmetic (a launch whose operands are not 16-byte addressable falls back to
 // the f32 kernel and re-plans within the workspace it is given)
@@ -1713,6 +1812,116 @@ ams_status ams_gemm_f32_at_b_colsum(int M, int N, int K, const float* A, long ld
     AMS_REQUIRE(g.a_vec && g.b_vec && M % 4 == 0 && N % 4 == 0 && aligned16(bsum_ws) && !tuning().novec);
     LaunchOpt o; o.amax_a = amax_a; o.amax_b = amax_b; o.lds_pad = lds_pad; o.sk_scratch = sk_scratch; o.sk_bytes = sk_bytes;
     return launch<A_COL, B_ROW>(g, o, ws, ws_bytes, (hipStream_t)stream, 1, bsum_out, bsum_accumulate, bsum_ws);
+}
+
+// ---- the three weight-gradient products of one BLSTM layer as ONE grouped launch (+ one finishing launch) ----
+// regions: 0 = wx (dK[0:D] (+)= x^T dz, column sums of dz), 1 = u_f (dK[D:, 0:4H] (+)= h_f[row]^T dz_f[row + 1]), 2 = u_b
+// (dK[D:, 4H:8H] (+)= h_b[row + 1]^T dz_b[row]); 128 x 256 tiles.  ONE slab count s for all of them, from the split model applied to
+// the whole tile count; k_per_split per region as launch() rounds it.  Workspace: the regions' slabs, then s rows of column-sum partials.
+struct BwGroupPlan { int M[3], N[3], K[3], splits[3], kps[3], tiles_m[3], tiles_n[3]; size_t slab_off[3], bsum_off, bytes; int n_items; };
+static bool bw_group_plan(int B, int T, int D, int H, BwGroupPlan& p) {
+    if (B <= 0 || T <= 0 || D <= 0 || H <= 0 || D % 4 || H % 4 || (long)B * T < 2 || (long)B * T >= (1L << 31) / (8L * H) ||
+        (long)(D + H) * 8 * H >= (1L << 31)) return false;
+    const TilePlan tp = x6_plan(3);
+    const int Kall = B * T;
+    const int M[3] = {D, H, H}, N[3] = {8 * H, 4 * H, 4 * H}, K[3] = {Kall, Kall - 1, Kall - 1};
+    int tiles = 0;
+    double elems = 0.0;
+    for (int r = 0; r < 3; ++r) {
+        p.M[r] = M[r]; p.N[r] = N[r]; p.K[r] = K[r];
+        p.tiles_m[r] = ceil_div(M[r], tp.bm); p.tiles_n[r] = ceil_div(N[r], tp.bn);
+        tiles += p.tiles_m[r] * p.tiles_n[r];
+        elems += (double)M[r] * N[r];
+    }
+    int s = choose_splits_tiles(tiles, elems, Kall, tp);
+    if (tuning().splits > 0) s = tuning().splits;
+    size_t off = 0;
+    p.n_items = 0;
+    for (int r = 0; r < 3; ++r) {
+        p.kps[r] = ceil_div(ceil_div(K[r], s), tp.bk) * tp.bk;
+        p.splits[r] = ceil_div(K[r], p.kps[r]);
+        p.slab_off[r] = off;
+        off += slab_bytes(M[r], N[r], 1, p.splits[r]);                 // (multiples of 16 bytes: N % 4 == 0)
+        p.n_items += p.tiles_m[r] * p.tiles_n[r] * p.splits[r];
+    }
+    p.bsum_off = off;
+    p.bytes = off + (size_t)p.splits[0] * N[0] * sizeof(float);
+    return true;
+}
+
+size_t ams_blstm_bwd_weights_workspace_bytes(int B, int T, int D, int H, int lds_pad) {
+    (void)lds_pad;                                   // capped and uncapped launches take the same plan
+    BwGroupPlan p;
+    return bw_group_plan(B, T, D, H, p) ? p.bytes : 0;
+}
+
+ams_status ams_blstm_bwd_weights_f32(int B, int T, int D, int H, const float* x, long ldx, const float* h, const float* dz, float* dK,
+                                     long ldk, float* db, int accumulate, const float* amax_x, const float* amax_h, const float* amax_dz,
+                                     int lds_pad, void* ws, size_t ws_bytes, void* stream) {
+    BwGroupPlan p;
+    AMS_REQUIRE(x && h && dz && dK && db && ws && bw_group_plan(B, T, D, H, p));
+    AMS_REQUIRE(aligned16(x) && aligned16(h) && aligned16(dz) && aligned16(dK) && aligned16(db) && aligned16(ws));
+    AMS_REQUIRE(ldk == 8L * H && ldx % 4 == 0 && ldx >= D);
+    AMS_REQUIRE((amax_x != nullptr) == (amax_h != nullptr) && (amax_x != nullptr) == (amax_dz != nullptr));
+    AMS_REQUIRE(use_x6() && !tuning().novec);          // the 16-bit-pipe kernel only: no other form of the grouped launch exists
+    if (ws_bytes < p.bytes) return AMS_E_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    const bool capped = lds_pad > 0;
+    const bool f16 = amax_x && tuning().f16x3;
+    float* const bsum_part = (float*)((char*)ws + p.bsum_off);
+
+    GemmArgs g{};
+    g.ldb = 8L * H; g.ldc = ldk;
+    g.accumulate = accumulate; g.bsum_accumulate = accumulate;
+    g.nbatch = 1;
+    g.a_vec = g.b_vec = g.c_vec = 1;
+    g.sk_rounds = -1;
+    g.hiprio = !capped;
+    g.amax_a = f16 ? amax_x : nullptr;
+    g.amax_b = f16 ? amax_dz : nullptr;
+    GroupTable t{};
+    const float* const A[3] = {x, h, h + 3L * H};
+    const float* const Bm[3] = {dz, dz + 8L * H, dz + 4L * H};
+    float* const C[3] = {dK, dK + (long)D * ldk, dK + (long)D * ldk + 4L * H};
+    const float* const am[3] = {amax_x, amax_h, amax_h};
+    GroupFinish f{};
+    bool finish = false;
+    for (int r = 0; r < 3; ++r) {
+        GroupRegion& q = t.r[r];
+        q.A = A[r]; q.B = Bm[r]; q.C = C[r]; q.amax_a = f16 ? am[r] : nullptr;
+        q.partial = (float*)((char*)ws + p.slab_off[r]);
+        q.lda = r == 0 ? ldx : 2L * H;
+        q.M = p.M[r]; q.N = p.N[r]; q.K = p.K[r];
+        q.mask_period = r == 0 ? 0 : T; q.mask_skip = r == 0 ? 0 : T - 1;
+        q.group_m = choose_group_m(p.tiles_m[r], p.tiles_n[r]);
+        q.splits = p.splits[r]; q.k_per_split = p.kps[r];
+        q.items = p.tiles_m[r] * p.tiles_n[r] * p.splits[r];
+        f.partial[r] = q.partial; f.C[r] = q.C; f.M[r] = q.M; f.N[r] = q.N; f.splits[r] = q.splits;
+        finish = finish || q.splits > 1;
+    }
+    t.r[0].bsum_part = bsum_part;                       // column sums of dz from the wx region's tile_m == 0 workgroups
+    t.r[0].bsum_out = p.splits[0] == 1 ? db : nullptr;  // the whole k range in one workgroup: finished inside the launch
+    t.n_items = p.n_items;
+
+    unsigned grid = (unsigned)p.n_items;
+    if (!capped && (long)grid > x6_persist_cap(3)) grid = (unsigned)x6_persist_cap(3);
+    if (f16) {
+        if (capped) hipLaunchKernelGGL((gemm_x6_group_kernel<false, true>), dim3(grid), dim3(512), 0, st, g, t);
+        else hipLaunchKernelGGL((gemm_x6_group_kernel<true, true>), dim3(grid), dim3(512), 0, st, g, t);
+    } else if (capped) hipLaunchKernelGGL((gemm_x6_group_kernel<false, false>), dim3(grid), dim3(512), 0, st, g, t);
+    else hipLaunchKernelGGL((gemm_x6_group_kernel<true, false>), dim3(grid), dim3(512), 0, st, g, t);
+    ams_status s = ams_check_launch();
+    if (s != AMS_OK || !finish) return s;
+    f.ldc = ldk; f.accumulate = accumulate;
+    f.bsum_part = bsum_part; f.bsum_out = db; f.bsum_n = 8 * H; f.bsum_splits = p.splits[0] > 1 ? p.splits[0] : 0;
+    int blocks = ceil_div(8 * H, 256);
+    for (int r = 0; r < 3; ++r) {
+        const int b = (int)(((long)p.M[r] * p.N[r] / 4 + 255) / 256);
+        if (p.splits[r] > 1 && b > blocks) blocks = b;
+    }
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(group_finish_kernel, dim3(blocks, 4), dim3(256), 0, st, f);
+    return ams_check_launch();
 }
 
 ams_status ams_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,

@@ -168,6 +168,27 @@ ams_status ams_gemm_f32_at_b_colsum(int M, int N, int K, const float* A, long ld
                                     int accumulate, float* bsum_out, int bsum_accumulate, float* bsum_ws, const float* amax_a,
                                     const float* amax_b, int lds_pad, void* ws, size_t ws_bytes, void* sk_scratch, size_t sk_bytes,
                                     void* stream);
+/* The three weight-gradient products of ONE BLSTM layer (utils/ops.py:358-383 under tf.gradients) as one grouped product launch plus
+ * one finishing launch (added under ABI 10: purely additive, no existing prototype or behaviour changes):
+ *   dK[0:D, 0:8H]      (+)= x^T . dz,  db[8H] (+)= column sums of dz                       (input kernels [Wx_f | Wx_b] and biases)
+ *   dK[D:D+H, 0:4H]    (+)= sum over rows r, r+1 of one utterance of h_f[r]^T . dz_f[r+1]  (recurrent kernel, forward direction)
+ *   dK[D:D+H, 4H:8H]   (+)= sum over the same row pairs of h_b[r+1]^T . dz_b[r]            (recurrent kernel, backward direction)
+ * x [B*T, D] (row pitch ldx), h [B*T, 2H] = (h_f | h_b), dz [B*T, 8H] = (dz_f 4H | dz_b 4H), dK the twin-interleaved gradient block
+ * [(D+H), 8H] with ldk == 8H, db the two adjacent bias gradients.  The 128 x 256 tile of ams_gemm_f32's 16-bit-pipe form: fp16x3 when
+ * all three bounds are given, bf16x6 when none is.  The k range is cut into ONE slab count for the three products (the split model
+ * applied to all their tiles; AMS_GEMM_SPLITS overrides it); with more than one slab the partial tiles go to ws and the finishing launch
+ * adds them in slab order, then the old value, and finishes the column sums -- given the same slab count, the bits of
+ * ams_gemm_f32_at_b_colsum + ams_gemm_f32_batched on the same operands.  lds_pad > 0: residency-capped (one item per workgroup).
+ * AMS_E_INVALID_ARG: D or H not a multiple of 4, ldk != 8H, ldx % 4 != 0, B*T < 2, a pointer (ws included) off a 16-byte boundary,
+ * bounds given only in part, or the process runs the native-f32 arithmetic (ams_gemm_set_arith(0), AMS_GEMM_NOVEC), for which no grouped form exists.
+ * AMS_E_WORKSPACE_TOO_SMALL: ws_bytes below ams_blstm_bwd_weights_workspace_bytes(same B, T, D, H, lds_pad).
+ * bound_x, bound_h, bound_dz: upper bounds of max|x|, max|h|, max|dz| as amax_a / amax_b of ams_gemm_f32 (three of them, hence not a
+ * PAIR of amax_* arguments: the range audit keys this launch's operands under the two product classes of the separate launches --
+ * ops.blstm_bwd_weights_grouped steps aside while an audit measures and passes no bounds once either class is denied). */
+size_t ams_blstm_bwd_weights_workspace_bytes(int B, int T, int D, int H, int lds_pad);
+ams_status ams_blstm_bwd_weights_f32(int B, int T, int D, int H, const float* x, long ldx, const float* h, const float* dz, float* dK,
+                                     long ldk, float* db, int accumulate, const float* bound_x, const float* bound_h, const float* bound_dz,
+                                     int lds_pad, void* ws, size_t ws_bytes, void* stream);
 /* ---- dilated 2-D convolution stack (ABI 7; csrc/conv2d.hip)      models/network.py:528-551 ----
  * One tf.contrib.layers.conv2d(y, cout, [kh, kw], rate=[rt, rf]) of Separator.dilated: stride 1, SAME, bias, ReLU.  Activations NHWC
  * [B, T, F, C] row-major (pixel p = (b T + t) F + f, channels fastest); weights HWIO [kh, kw, cin, cout]; kh, kw odd, tap (i, j) reads
