@@ -11,7 +11,8 @@
 // in (chunk, wavefront) order.  (The SOFT modes, which are tolerance-checked, keep 2048-point chunks and one 256-lane tree: their
 // 64 rows would not fill the device with 8192-point workgroups.)  Everything that is compared bit for bit
 // (hard distances, normalisation, inertia) accumulates left-to-right with separate, individually rounded multiply and add (no contraction), sqrt is IEEE,
-// ties pick the lowest cluster (tf.argmin).
+// ties pick the lowest cluster (tf.argmin); a NaN distance or inertia is taken as np.argmin in the oracle takes it: the first NaN wins
+// (TF leaves that case unspecified).
 //
 // Algorithmic bytes per pass: L*E*4 per row (+ L*4 weights); x[b] is shared by the `tries` rows of an utterance
 // through L2.
@@ -77,7 +78,19 @@ struct KmArgs {
     // kmeans_reduce_kernel did in a launch of its own, ~5 us + a kernel boundary on the serial chain of each of the 11 passes
     unsigned* tickets;     // [R], zero on entry, left zero
     float* fin_out; float* fin_den;
+#ifdef AMS_KM_RAGGED
+    // ragged build (csrc/kmeans_ragged/, include/ams_kmeans_ragged.h): the utterances are SEGMENTS of different lengths packed in xn; a
+    // workgroup takes its unit of work from the host-built table instead of computing it from blockIdx.  b = segments; L and G unused.
+    const int32_t* tab;    // [4 Gtot, 4]: (segment, chunk, column, 0), the four columns of a chunk adjacent
+    const long* p_off;     // [b + 1]: segment s holds the points p_off[s] .. p_off[s + 1]
+    const long* g_off;     // [b + 1]: its 8192-point chunks are g_off[s] .. g_off[s + 1] of the Gtot in all
+    int Gtot;
+#endif
 };
+#ifdef AMS_KM_RAGGED
+typedef const __attribute__((address_space(4))) int32_t km_cint;         // the tables are uniform reads: scalar loads
+typedef const __attribute__((address_space(4))) long km_clong;
+#endif
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -108,7 +121,11 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     constexpr bool SOFT = (MODE == SOFT_ACC || MODE == SOFT_FINAL);
     constexpr int NV = ACC ? C_ * (E_ + 1) : 2 * C_;
     // labels alone have no summation order to keep: the small chunks, which fill the device when R = b (the re-assignment at the end)
+#ifdef AMS_KM_RAGGED
+    constexpr int CHUNK = CHUNK_HARD, PPL = CHUNK / LANES;         // the table's chunks, in every mode
+#else
     constexpr int CHUNK = chunk_of(SOFT || MODE == HARD_LABELS), PPL = CHUNK / LANES;
+#endif
     constexpr int LD = E_ + 4;                     // 16-byte aligned rows; 16 lanes x 16 B at this pitch cover all 64 banks
     constexpr int V4 = E_ / 4, V2 = E_ / 2;
     constexpr int BUF = (256 * LD > 128 * 64) ? 256 * LD : 128 * 64;
@@ -120,6 +137,21 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     // XCD's 4 MB L2 while its 10 tries read them.  In (chunk, row) order every try's read went out to the fabric: 2.1 GB per pass
     // at the benchmark shape, a prefetched slab took ~6 us to arrive and the waves sat idle 55 % of the time (-DAMS_KM_TRACE).
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    constexpr int NPW = SOFT ? 1 : 4;                              // partial rows per workgroup
+#ifdef AMS_KM_RAGGED
+    // workgroup -> (chunk of a segment, try) through the table, the tries of a chunk adjacent (they read the same points); the segment's
+    // own length, chunk count and place among the partial rows take the place of L, G and r G
+    const int u = blockIdx.x / a.tries, tr_ = blockIdx.x - u * a.tries;
+    const int sg = ((km_cint*)a.tab)[16 * u], g = ((km_cint*)a.tab)[16 * u + 1];     // the entry of the chunk's column 0
+    const long sp0 = ((km_clong*)a.p_off)[sg], seg_L = ((km_clong*)a.p_off)[sg + 1] - sp0;
+    const long gp0 = ((km_clong*)a.g_off)[sg];
+    const int seg_G = (int)(((km_clong*)a.g_off)[sg + 1] - gp0);
+    const int r = sg * a.tries + tr_;
+    const long prow0 = (gp0 * a.tries + (long)tr_ * seg_G) * NPW;  // the row's first partial row
+    const long lab0 = sp0;                                         // (label passes run with tries = 1: labels [Ptot])
+    const float* xb = a.xn + sp0 * E_;
+    const float* wb = HAS_W ? a.w + sp0 : nullptr;
+#else
     int r, g;
     {
         const int M = a.G * a.tries, xcd = blockIdx.x & 7, n = blockIdx.x >> 3;
@@ -131,6 +163,9 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     const int bi = r / a.tries;
     const float* xb = a.xn + (long)bi * a.L * E_;
     const float* wb = HAS_W ? a.w + (long)(a.w_mod_b ? (r % a.b) : bi) * a.L : nullptr;
+    const long seg_L = a.L, prow0 = (long)r * a.G * NPW, lab0 = (long)r * a.L;
+    const int seg_G = a.G;
+#endif
     for (int i = tid; i < C_ * E_; i += 256) scent[i] = a.cent[(long)r * C_ * E_ + i];
 #if AMS_KM_SGPR_CENT
     // HARD modes: the row's centroids are wave-uniform -> held in SGPRs (C*E = 80 scalars at E = 40, C = 2) and fed to the packed
@@ -156,7 +191,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     float4 pre[V4];
     auto fetch = [&](int j) {
         const long q0 = (long)g * CHUNK + (long)j * LANES + wave * 64;
-        const int np = (int)max((long)0, min((long)64, a.L - q0));
+        const int np = (int)max((long)0, min((long)64, seg_L - q0));
         const float4* src = reinterpret_cast<const float4*>(xb + q0 * E_);
 #pragma unroll
         for (int k = 0; k < V4; ++k) {
@@ -175,7 +210,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     float* wbuf = buf + wave * 64 * LD;
     for (int j = 0; j < PPL; ++j) {
         const long p0 = (long)g * CHUNK + (long)j * LANES;
-        const int npts = (int)max((long)0, min((long)LANES, a.L - p0));
+        const int npts = (int)max((long)0, min((long)LANES, seg_L - p0));
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // this wave's reads of the previous slab are complete
         __builtin_amdgcn_wave_barrier();
         if (!PF) fetch(j);
@@ -289,7 +324,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
 #pragma unroll
                 for (int c = 1; c < C_; ++c) {
                     const float dc = sqrtf(d2[c]);
-                    if (dc < best) { best = dc; lab = c; }
+                    if (best == best && !(best <= dc)) { best = dc; lab = c; }      // nearer, or the first NaN (np.argmin: oracle/kmeans.py)
                 }
                 if (MODE == HARD_ACC) {
                     f2 mm[C_];
@@ -332,7 +367,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
                     };
                     if (HAS_W) accum(std::true_type{}); else accum(std::false_type{});
                 } else if (MODE == HARD_LABELS) {
-                    a.labels[(long)r * a.L + p0 + tid] = lab;
+                    a.labels[lab0 + p0 + tid] = lab;
                 } else {
                     // inertia terms: unweighted distance to the assigned centroid (Kmeans_2.py:131-136)
                     float dist = 0.f;
@@ -354,7 +389,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
                         acc[c] = __fadd_rn(acc[c], __fmul_rn(dist, m));
                         acc[C_ + c] = __fadd_rn(acc[C_ + c], m);
                     }
-                    if (a.labels) a.labels[(long)r * a.L + p0 + tid] = lab;
+                    if (a.labels) a.labels[lab0 + p0 + tid] = lab;
                 }
             } else {
                 float ex[C_], sum = 0.f;
@@ -393,7 +428,6 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
             }
         }
     }
-    constexpr int NPW = SOFT ? 1 : 4;                              // partial rows per workgroup
     if (MODE == HARD_LABELS) return;
     if (!SOFT) {
         // HARD modes: every wavefront is a partial of its own -- lanes combined by the halving tree l += l + s (s = 32 .. 1) on the VALU
@@ -409,7 +443,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
             v = __fadd_rn(v, lane_above<2>(v));
             v = __fadd_rn(v, lane_above<1>(v));
             if (lane == 0) {
-                float* const dst = a.part + (((long)r * a.G + g) * 4 + wave) * NV + i;
+                float* const dst = a.part + (prow0 + (long)g * 4 + wave) * NV + i;
                 if (a.tickets) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through: read by the finisher
                 else *dst = v;
             }
@@ -457,7 +491,7 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
             v = __fadd_rn(v, lane_above<2>(v));
             v = __fadd_rn(v, lane_above<1>(v));
             if (lane == 0) {
-                float* const dst = a.part + ((long)r * a.G + g) * NV + i;
+                float* const dst = a.part + (prow0 + g) * NV + i;
                 if (a.tickets) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through: read by the finisher
                 else *dst = v;
             }
@@ -472,14 +506,14 @@ __global__ __launch_bounds__(256, (MODE == HARD_ACC || MODE == HARD_FINAL || MOD
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int last = atomicAdd(a.tickets + r, 1u) == (unsigned)a.G - 1u;
+        const int last = atomicAdd(a.tickets + r, 1u) == (unsigned)seg_G - 1u;
         if (last) __hip_atomic_store(a.tickets + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last_sh = last;
     }
     __syncthreads();
     if (!last_sh) return;
-    const int NP = a.G * NPW;
-    const float* pr = a.part + (long)r * NP * NV;
+    const int NP = seg_G * NPW;
+    const float* pr = a.part + prow0 * NV;
     // chunk partials fetched EIGHT AT A TIME and then added in chunk order: as one dependent chain of agent-scope loads per element the
     // finish put ~20 us at the end of every pass (225 us instead of 199 + a 5-us reduce launch)
     auto chunk_sum = [&](int k) {
@@ -547,6 +581,17 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
     constexpr int LD = E_ + 4, V4 = E_ / 4;
     __shared__ __attribute__((aligned(16))) float buf[256 * LD];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#ifdef AMS_KM_RAGGED
+    const int u = blockIdx.x / a.tries, tr_ = blockIdx.x - u * a.tries;      // the table's unit: see kmeans_pass_kernel
+    const int sg = ((km_cint*)a.tab)[16 * u], g = ((km_cint*)a.tab)[16 * u + 1];
+    const long sp0 = ((km_clong*)a.p_off)[sg], seg_L = ((km_clong*)a.p_off)[sg + 1] - sp0;
+    const long gp0 = ((km_clong*)a.g_off)[sg];
+    const int seg_G = (int)(((km_clong*)a.g_off)[sg + 1] - gp0);
+    const int r = sg * a.tries + tr_;
+    const long prow0 = (gp0 * a.tries + (long)tr_ * seg_G) * 4;
+    const float* xb = a.xn + sp0 * E_;
+    const float* wb = HAS_W ? a.w + sp0 : nullptr;
+#else
     int r, g;
     {
         const int M = a.G * a.tries, xcd = blockIdx.x & 7, n = blockIdx.x >> 3;
@@ -558,6 +603,9 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
     const int bi = r / a.tries;
     const float* xb = a.xn + (long)bi * a.L * E_;
     const float* wb = HAS_W ? a.w + (long)(a.w_mod_b ? (r % a.b) : bi) * a.L : nullptr;
+    const long seg_L = a.L, prow0 = (long)r * a.G * 4;
+    const int seg_G = a.G;
+#endif
     unsigned long long lab_lo = 0ull, lab_hi = 0ull;               // labels of this lane's points j = 0..15 / 16..31
     float* wbuf = buf + wave * 64 * LD;
 
@@ -577,7 +625,7 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
         float4 pre[V4];
         auto fetch = [&](int j) {
             const long q0 = (long)g * CHUNK + (long)j * LANES + wave * 64;
-            const int np = (int)max((long)0, min((long)64, a.L - q0));
+            const int np = (int)max((long)0, min((long)64, seg_L - q0));
             const float4* src = reinterpret_cast<const float4*>(xb + q0 * E_);
 #pragma unroll
             for (int k = 0; k < V4; ++k) {
@@ -588,7 +636,7 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
         fetch(0);
         for (int j = 0; j < PPL; ++j) {
             const long p0 = (long)g * CHUNK + (long)j * LANES;
-            const int npts = (int)max((long)0, min((long)LANES, a.L - p0));
+            const int npts = (int)max((long)0, min((long)LANES, seg_L - p0));
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // this wave's reads of the previous slab are complete
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -639,7 +687,7 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
 #pragma unroll
                     for (int c = 1; c < C_; ++c) {
                         const float dc = sqrtf((c & 1) ? dp[c / 2].y : dp[c / 2].x);
-                        if (dc < best) { best = dc; lab = c; }
+                        if (best == best && !(best <= dc)) { best = dc; lab = c; }      // nearer, or the first NaN (np.argmin: oracle/kmeans.py)
                     }
                     const unsigned long long bits = (unsigned long long)lab << (4 * (j & 15));
                     if (j < 16) lab_lo |= bits; else lab_hi |= bits;
@@ -688,7 +736,7 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
             v = __fadd_rn(v, lane_above<1>(v));
             if (lane == 0) {
                 const int k = i < CN * E_ ? C0 * E_ + i : C_ * E_ + C0 + (i - CN * E_);
-                float* const dst = a.part + (((long)r * a.G + g) * 4 + wave) * NV + k;
+                float* const dst = a.part + (prow0 + (long)g * 4 + wave) * NV + k;
                 if (a.tickets) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through: read by the finisher
                 else *dst = v;
             }
@@ -704,15 +752,15 @@ __global__ __launch_bounds__(256, AMS_KM_WAVES) void kmeans_hard_acc_grouped_ker
     if (tid == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int last = atomicAdd(a.tickets + r, 1u) == (unsigned)a.G - 1u;
+        const int last = atomicAdd(a.tickets + r, 1u) == (unsigned)seg_G - 1u;
         if (last) __hip_atomic_store(a.tickets + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last_sh = last;
     }
     __syncthreads();
     if (!last_sh || tid >= C_ * E_) return;
     // the row's last chunk: its 4 G partial rows added in (chunk, wavefront) order, eight loads in flight (kmeans_pass_kernel)
-    const int NP = a.G * 4;
-    const float* pr = a.part + (long)r * NP * NV;
+    const int NP = seg_G * 4;
+    const float* pr = a.part + prow0 * NV;
     auto chunk_sum = [&](int k) {
         float s = 0.f;
         int gg = 0;
@@ -787,6 +835,9 @@ struct KtArgs {
     int32_t* labels;                   // kmeans_hard_tries_final_kernel: [R, L] or null
     const float* w; int w_mod_b;       // silence weights [b, L] or null; row of try r: r % b (the reference's tile quirk) or r / tries
     unsigned long long* dbg;           // AMS_KT_DBG builds: per (workgroup, wave) {HW_ID | XCC_ID << 32, start, end} (s_memrealtime)
+#ifdef AMS_KM_RAGGED
+    const int32_t* tab; const long* p_off; const long* g_off;      // the work table and the segments: see KmArgs (b = segments; L, G unused)
+#endif
 };
 
 // one component of the packed distance chains: df = {x - c0, x - c1} with x broadcast from the low (KT_LO) or high (KT_HI) half of a
@@ -856,12 +907,21 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     // workgroup -> (utterance, try group, column, chunk), the chunk slowest: a short last chunk's workgroups come last
     int id = blockIdx.x;
     const int ntg = a.tries / TQ;
+#ifdef AMS_KM_RAGGED
+    // workgroup -> (try group, unit of the table), the try groups of a unit adjacent: (segment, chunk, column) is read, not computed
+    const int tg = id % ntg; id /= ntg;
+    const int ub = ((km_cint*)a.tab)[4 * id], g = ((km_cint*)a.tab)[4 * id + 1], k4 = ((km_cint*)a.tab)[4 * id + 2];
+    const long sp0 = ((km_clong*)a.p_off)[ub], seg_L = ((km_clong*)a.p_off)[ub + 1] - sp0;
+    const float* xb = a.xn + sp0 * E_;
+#else
     const int ub = id % a.b; id /= a.b;
     const int tg = id % ntg; id /= ntg;
     const int k4 = id & 3, g = id >> 2;
     const float* xb = a.xn + (long)ub * a.L * E_;
+    const long seg_L = a.L;
+#endif
     const long base = (long)g * CHUNK_HARD + k4 * 64;              // slab i of this column: points base + 256 i .. + 63
-    const long left = a.L - base;
+    const long left = seg_L - base;
     const int nsl = left <= 0 ? 0 : (int)min((long)SL, (left + LANES - 1) / LANES);
     const int nit = (nsl + 1) / 2;
     const int row0 = ub * a.tries + tg * TQ;
@@ -889,7 +949,12 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     float w_nxt = 1.0f;
     if constexpr (HAS_W) {
         const int r1 = row0 + tt;
+#ifdef AMS_KM_RAGGED
+        (void)r1;
+        wrs = make_rsrc(a.w + sp0, (unsigned)(seg_L * 4));           // weight row = segment
+#else
         wrs = make_rsrc(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L, (unsigned)(a.L * 4));
+#endif
         w_nxt = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, (unsigned)((base + (long)kk * LANES + lane) * 4), 0, 0));
     }
     // sums role
@@ -904,7 +969,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     // staging: thread -> (point pr of a slab, 16-byte group c4) of BOTH slabs of an iteration
     const int pr = tid / V4, c4 = tid - pr * V4;
     // the utterance as a buffer resource: 32-bit offsets, and rows past L come back as zeros without a test (raw buffer bounds check)
-    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(a.L * E_ * 4));
+    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(seg_L * E_ * 4));
     float4 pf[2];
     unsigned foff = (unsigned)((base + pr) * E_ + c4 * 4) * 4u;   // byte offset of this thread's group in slab 0 of the column
     auto fetch = [&](int it) {
@@ -992,7 +1057,9 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
                     KT_DIST(dp, xhi, KT_LO, cpair[4 * q4 + 2]); KT_DIST(dp, xhi, KT_HI, cpair[4 * q4 + 3]);
                 }
             }
-            const bool one = sqrtf(dp.y) < sqrtf(dp.x);            // ties pick cluster 0 (tf.argmin)
+            // ties pick cluster 0 (tf.argmin); a NaN distance (a NaN centroid: an empty cluster) wins as it does in np.argmin, the first one if both are
+            const float s0 = sqrtf(dp.x), s1 = sqrtf(dp.y);
+            const bool one = s0 == s0 && !(s0 <= s1);
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(one);
             const unsigned long long valid = valid_of(2 * it + kk);
             mf[cur][kk][tt][lane] = mask_to_float(bal & valid);
@@ -1020,7 +1087,15 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
 #ifdef AMS_KT_DBG
     unsigned long long* const a_dbg = ka->dbg;
 #endif
+#ifdef AMS_KM_RAGGED
+    // the segment's chunk count and its place among the partial rows, read only here (scalar registers are short in the loop)
+    const long gp0_ = ((km_clong*)ka->g_off)[ub];
+    const int NP = 4 * (int)(((km_clong*)ka->g_off)[ub + 1] - gp0_), pi = g * 4 + k4;
+    const long prow0 = 4 * gp0_ * ka->tries + (long)(tg * TQ) * NP;       // first partial row of try row0
+#else
     const int NP = 4 * ka->G, pi = g * 4 + k4;
+    const long prow0 = (long)row0 * NP;
+#endif
     const int jl = ((lane >> 4) & 1) * 2 + (lane >> 5);            // lanes 0 / 16 / 32 / 48 hold components 0 / 2 / 1 / 3 of a group
 #pragma unroll
     for (int t = 0; t < TQ; ++t)
@@ -1028,7 +1103,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
         for (int c = 0; c < C_; ++c) {
             const float v = tree4(acc[t][c][0], acc[t][c][1], acc[t][c][2], acc[t][c][3]);
             if ((lane & 15) == 0)
-                __hip_atomic_store(a_part + ((long)(row0 + t) * NP + pi) * NV + c * E_ + wave * 4 + jl, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a_part + (prow0 + (long)t * NP + pi) * NV + c * E_ + wave * 4 + jl, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 #ifdef AMS_KT_DBG
     if (a_dbg && lane == 0) {
@@ -1046,7 +1121,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     __syncthreads();
     if (kk == 0 && lane < C_) {
         const int tot = (lane == 0 ? n0 : n1) + cbuf[tt][lane];
-        __hip_atomic_store(a_part + ((long)(row0 + tt) * NP + pi) * NV + C_ * E_ + lane, (float)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a_part + (prow0 + (long)tt * NP + pi) * NV + C_ * E_ + lane, (float)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (a_tickets == nullptr) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's partials are acknowledged
@@ -1062,7 +1137,7 @@ __global__ __launch_bounds__(640, AMS_KT_WAVES) void kmeans_hard_tries_kernel(Kt
     const int ft = tid / (C_ * E_), fk = tid - ft * (C_ * E_);
     if (ft >= TQ || !last_sh[ft]) return;
     const int r = row0 + ft;
-    const float* prr = a_part + (long)r * NP * NV;
+    const float* prr = a_part + (prow0 + (long)ft * NP) * NV;
     auto chunk_sum = [&](int k) {
         float s = 0.f;
         for (int gg = 0; gg < NP; gg += 8) {
@@ -1094,12 +1169,21 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     int id = blockIdx.x;
     const int ntg = a.tries / TQ;
+#ifdef AMS_KM_RAGGED
+    // workgroup -> (try group, column PAIR of the table): the entry of the pair's even column
+    const int tg = id % ntg; id /= ntg;
+    const int ub = ((km_cint*)a.tab)[8 * id], g = ((km_cint*)a.tab)[8 * id + 1], cp = ((km_cint*)a.tab)[8 * id + 2] >> 1;
+    const long sp0 = ((km_clong*)a.p_off)[ub], seg_L = ((km_clong*)a.p_off)[ub + 1] - sp0;
+    const float* xb = a.xn + sp0 * E_;
+#else
     const int ub = id % a.b; id /= a.b;
     const int tg = id % ntg; id /= ntg;
     const int cp = id & 1, g = id >> 1;
     const float* xb = a.xn + (long)ub * a.L * E_;
+    const long seg_L = a.L;
+#endif
     const long base = (long)g * CHUNK_HARD + cp * 128;             // slab i of the column pair: points base + 256 i .. + 127
-    const long left = a.L - base;
+    const long left = seg_L - base;
     const int nit = left <= 0 ? 0 : (int)min((long)SL, (left + LANES - 1) / LANES);
     const int left32 = (int)min(max(left, (long)0), (long)(SL * LANES));
     const int row0 = ub * a.tries + tg * TQ;
@@ -1122,11 +1206,16 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
     float w_nxt = 1.0f;
     if constexpr (HAS_W) {                                          // silence weights: the LABELS are weighted, the inertia distance is not
         const int r1 = row0 + tt;
+#ifdef AMS_KM_RAGGED
+        (void)r1;
+        wrs = make_rsrc(a.w + sp0, (unsigned)(seg_L * 4));           // weight row = segment
+#else
         wrs = make_rsrc(a.w + (long)(a.w_mod_b ? (r1 % a.b) : ub) * a.L, (unsigned)(a.L * 4));
+#endif
         w_nxt = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wrs, (unsigned)((base + kk * 64 + lane) * 4), 0, 0));
     }
     const int pr = tid / V4, c4 = tid - pr * V4;
-    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(a.L * E_ * 4));
+    const __amdgpu_buffer_rsrc_t xrs = make_rsrc(xb, (unsigned)(seg_L * E_ * 4));
     float4 pf[2];
     const unsigned foff = (unsigned)((base + pr) * E_ + c4 * 4) * 4u;
     auto fetch = [&](int it) {
@@ -1148,7 +1237,11 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
         if (nit > 1) fetch(1);
     }
     __syncthreads();
+#ifdef AMS_KM_RAGGED
+    int32_t* const lrow = nullptr;                                 // (the ragged run takes its labels from a pass of their own)
+#else
     int32_t* const lrow = a.labels ? a.labels + (long)(row0 + tt) * a.L + base + kk * 64 + lane : nullptr;
+#endif
     for (int it = 0; it < nit; ++it) {
         const int cur = it & 1;
         const float wv = w_nxt;
@@ -1176,7 +1269,8 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
             }
         }
         if constexpr (!HAS_W) dq = dp;
-        const bool one = sqrtf(dp.y) < sqrtf(dp.x);
+        const float s0 = sqrtf(dp.x), s1 = sqrtf(dp.y);
+        const bool one = s0 == s0 && !(s0 <= s1);              // (kmeans_hard_tries_kernel: nearer, or the first NaN)
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(one);
         const unsigned long long valid = valid_of(it);
         n1 += __builtin_popcountll(bal & valid);
@@ -1198,9 +1292,16 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
     const __attribute__((address_space(4))) KtArgs* ka = (const __attribute__((address_space(4))) KtArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
     float* const a_part = ka->part; unsigned* const a_tickets = ka->tickets; float* const a_fin_out = ka->fin_out;
+#ifdef AMS_KM_RAGGED
+    const long gp0_ = ((km_clong*)ka->g_off)[ub];
+    const int NP = 4 * (int)(((km_clong*)ka->g_off)[ub + 1] - gp0_), pi = g * 4 + cp * 2 + kk;
+    const long prow0 = 4 * gp0_ * ka->tries + (long)(tg * TQ) * NP;       // first partial row of try row0 (kmeans_hard_tries_kernel)
+#else
     const int NP = 4 * ka->G, pi = g * 4 + cp * 2 + kk;
+    const long prow0 = (long)row0 * NP;
+#endif
     {
-        float* const dst = a_part + ((long)(row0 + tt) * NP + pi) * NVF;
+        float* const dst = a_part + (prow0 + (long)tt * NP + pi) * NVF;
         const float v = tree4(tot0, tot1, 0.f, 0.f);               // lanes 0 / 32: tot of cluster 0 / 1
         if ((lane & 31) == 0) __hip_atomic_store(dst + (lane >> 5), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane < C_) __hip_atomic_store(dst + C_ + lane, (float)(lane == 0 ? n0 : n1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1219,7 +1320,7 @@ __global__ __launch_bounds__(640, 6) void kmeans_hard_tries_final_kernel(KtArgs 
     const int ft = tid >> 1, c = tid & 1;
     if (ft >= TQ || !last_sh[ft]) return;
     const int r = row0 + ft;
-    const float* prr = a_part + (long)r * NP * NVF;
+    const float* prr = a_part + (prow0 + (long)ft * NP) * NVF;
     auto chunk_sum = [&](int k) {
         float s = 0.f;
         for (int gg = 0; gg < NP; gg += 8) {
@@ -1396,7 +1497,7 @@ __global__ void kmeans_select_kernel(const float* __restrict__ inertia, const fl
     float bv = inertia[(long)bi * tries];
     for (int t = 1; t < tries; ++t) {
         const float v = inertia[(long)bi * tries + t];
-        if (v < bv) { bv = v; bt = t; }
+        if (bv == bv && !(bv <= v)) { bv = v; bt = t; }           // first minimum; the first NaN if there is one (np.argmin)
     }
     if (threadIdx.x == 0) best[bi] = bt;
     for (int i = threadIdx.x; i < CE; i += blockDim.x) sel[(long)bi * CE + i] = cent[((long)bi * tries + bt) * CE + i];
@@ -1405,7 +1506,11 @@ __global__ void kmeans_select_kernel(const float* __restrict__ inertia, const fl
 
 template <int MODE>
 ams_status launch_pass(const KmArgs& a, int R, int E, int C, hipStream_t st) {
+#ifdef AMS_KM_RAGGED
+    dim3 grid((unsigned)((long)a.Gtot * a.tries));                 // one workgroup per (chunk of the table, try)
+#else
     dim3 grid((unsigned)(ceil_div(a.b, 8) * 8 * a.G * a.tries));   // flat: see the work order at the top of kmeans_pass_kernel
+#endif
     const bool hw = a.w != nullptr;
 #define AMS_KM(EE, CC) do { if (hw) hipLaunchKernelGGL((kmeans_pass_kernel<EE, CC, MODE, true>), grid, dim3(256), 0, st, a); \
                             else hipLaunchKernelGGL((kmeans_pass_kernel<EE, CC, MODE, false>), grid, dim3(256), 0, st, a); } while (0)
@@ -1428,6 +1533,7 @@ ams_status launch_pass(const KmArgs& a, int R, int E, int C, hipStream_t st) {
 
 }  // namespace
 
+#ifndef AMS_KM_RAGGED          // (the ragged build has entry points of its own: csrc/kmeans_ragged/kmeans_ragged.hip)
 extern "C" {
 
 ams_status ams_kmeans_normalize(const float* x, float* xn, long nrows, int E, void* stream) {
@@ -1578,3 +1684,4 @@ ams_status ams_kmeans_select(const float* inertia, const float* centroids, int32
 }
 
 }  // extern "C"
+#endif

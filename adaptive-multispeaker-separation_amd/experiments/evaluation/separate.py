@@ -35,6 +35,9 @@ def build_parser():
                           required=False, default=None)
     p.parser.add_argument('--input_rate', type=int, help='Sample rate of an .npy input (required with --resample and .npy)',
                           required=False, default=None)
+    p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
+                          "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
+                          "(hard k-means only; DESIGN.md 4.10)")
     p.add_adapt_args()
     p.add_separator_args()
     return p
@@ -134,7 +137,7 @@ def main(argv=None):
     tr = inferencer(sep, 'inference', **vars(args))
     model = tr.prepare_inference()
     with tr.graph.as_default():
-        out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs).cpu().numpy()
+        out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs, clustering=args.clustering).cpu().numpy()
     paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'), out_fs)
     print('\n'.join(paths))
     return paths

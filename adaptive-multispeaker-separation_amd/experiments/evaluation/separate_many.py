@@ -35,6 +35,9 @@ def build_parser():
                           'to %d Hz, separate, and resample the outputs back, all on the GPU' % config.fs)
     p.parser.add_argument('--output_rate', type=int, help='Sample rate of the outputs with --resample (default: the rate of each input)',
                           required=False, default=None)
+    p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
+                          "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
+                          "(hard k-means only; DESIGN.md 4.10)")
     p.add_adapt_args()
     p.add_separator_args()
     return p
@@ -111,11 +114,12 @@ def main(argv=None):
         if args.resample:
             for fs in sorted(set(fs for _, fs in recs)):          # the files of one rate together
                 idx = [i for i, (_, f) in enumerate(recs) if f == fs]
-                res = model.separate_recordings([recs[i][0] for i in idx], hop=args.hop, fs=fs, output_fs=args.output_rate)
+                res = model.separate_recordings([recs[i][0] for i in idx], hop=args.hop, fs=fs, output_fs=args.output_rate,
+                                                clustering=args.clustering)
                 for i, o in zip(idx, res):
                     outs[i] = o.cpu().numpy()
         else:
-            outs = [o.cpu().numpy() for o in model.separate_recordings([x for x, _ in recs], hop=args.hop)]
+            outs = [o.cpu().numpy() for o in model.separate_recordings([x for x, _ in recs], hop=args.hop, clustering=args.clustering)]
     os.makedirs(args.output_dir, exist_ok=True)
     written = []
     for p, (_, fs), out in zip(paths, recs, outs):

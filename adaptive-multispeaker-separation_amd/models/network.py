@@ -524,7 +524,8 @@ class Network(object):
         # (pre: the word is up already -- a ring evaluation would be run, thrown away and leave nothing new to learn: straight to the
         # per-step kernels, one collective per batch instead of two)
         if K.LSTM_RING != '0' and (pre or self._ring_error_any()):
-            ins = self._inputs_of(run)
+            # (every fed node is fed again: infer_chunks_masked also feeds the separator's masks)
+            ins = self._inputs_of(run) + [(n, t) for n, t in inputs or () if all(n is not m for m in (self.x_mix, self.x_non_mix, self.I))]
             if not pre:
                 K.ring_errors_clear()
             old, K.LSTM_RING = K.LSTM_RING, '0'
@@ -614,9 +615,194 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
-    def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None):
+    # ---- recording-level clustering: the embeddings of ALL chunks of a recording are one point set for one k-means,
+    # so every chunk shares its centroids and the labels mean the same speaker everywhere: no border permutation is left to decide
+    CLUSTER_CAP_BYTES = 8 << 30                # packed points (Ctot TF E 4 bytes) clustered at a time, unless the caller says otherwise
+
+    def _clustering_separator(self):
+        """(separator, its KMeans) of a model that separates by k-means on embeddings; ValueError otherwise."""
+        sep = getattr(self, 'sepNet', None) or self
+        km = getattr(sep, 'kmeans', None)
+        if km is None or getattr(sep, 'embeddings', None) is None or getattr(sep, 'masks', None) is None:
+            raise ValueError("clustering='recording' needs a model with a k-means separator (`separate` on embeddings); this one has none")
+        return sep, km
+
+    def _check_clustering(self, clustering, kmeans_init_indices, R):
+        """The refusals of the clustering arguments, all before anything is uploaded.  Returns the seeds as a list of R int32 [tries, C]
+        host arrays (None: to be drawn)."""
+        if clustering not in ('chunk', 'recording'):
+            raise ValueError("clustering must be 'chunk' or 'recording', got %r" % (clustering,))
+        if clustering == 'chunk':
+            if kmeans_init_indices is not None:
+                raise ValueError("kmeans_init_indices are the per-recording seeds of clustering='recording'; the per-chunk seeds of "
+                                 "clustering='chunk' belong to the model (--kmeans_init_indices)")
+            return None
+        sep, km = self._clustering_separator()
+        if km.beta is not None:
+            raise ValueError("clustering='recording' is hard assignment only: this model runs a soft k-means (beta_kmeans = %r)" % (km.beta,))
+        if kmeans_init_indices is None:
+            return None
+        seeds = list(kmeans_init_indices) if hasattr(kmeans_init_indices, '__len__') and not torch.is_tensor(kmeans_init_indices) else None
+        if seeds is None or len(seeds) != R:
+            raise ValueError('kmeans_init_indices: a list of one [tries, clusters] array per recording (%d), got %s'
+                             % (R, type(kmeans_init_indices).__name__ if seeds is None else 'a list of %d' % len(seeds)))
+        out = []
+        for r, v in enumerate(seeds):
+            v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+            if v.dtype.kind not in 'iu' or v.shape != (km.nb_tries, km.nb_clusters):
+                raise ValueError('kmeans_init_indices[%d]: integers of shape [tries, clusters] = [%d, %d], got %s %s'
+                                 % (r, km.nb_tries, km.nb_clusters, v.dtype, v.shape))
+            out.append(v.astype(np.int32))
+        return out
+
+    def _chunk_batches(self, mix, batch_size, what):
+        """The batches infer_chunks makes of mix [C, L]: (first chunk, chunks that count, the fed inputs) per model pass."""
+        self._refuse_unless_separating()
+        B = int(batch_size or self.args['batch_size'])
+        if mix.dim() != 2 or mix.shape[1] != self.args['chunk_size']:
+            raise ValueError('%s: chunks of %s samples for a model built with chunk_size %d'
+                             % (what, tuple(mix.shape)[1:], self.args['chunk_size']))
+        if B < 1 or mix.shape[0] < 1:
+            raise ValueError('%s: needs at least one chunk and a batch size of at least 1' % what)
+        C, L = mix.shape
+        xn = torch.zeros((B, self.S, L), dtype=mix.dtype, device=mix.device)
+        ind = torch.zeros((B, self.S), dtype=torch.int32, device=mix.device)
+        for b0 in range(0, C, B):
+            xm = mix[b0:b0 + B]
+            n = xm.shape[0]
+            if n < B:
+                xm = torch.cat([xm, xm[-1:].expand(B - n, L)], dim=0)
+            yield b0, n, [(self.x_mix, xm.contiguous()), (self.x_non_mix, xn), (self.I, ind)]
+
+    def _embed_batches(self, mix, batch_size):
+        """Pass 1, one model pass per batch: (first chunk, chunks that count, points [B, TF, E], weights [B, TF] or None).  The points
+        are normalised exactly as the model's KMeans normalises them (ams_hip/kmeans_host.py: _run), the one-pass form of the Normalize
+        layer and the k-means' own normalisation where it applies; the silence weights are per chunk, as there."""
+        sep, km = self._clustering_separator()
+
+        def points(run):
+            if km.pre_norm is not None and km.normalize_input:
+                node, E = km.pre_norm
+                u = node.value(run)
+                xn = K.l2norm_kmeans_normalize(F._c(u.reshape(u.shape[0], -1, E)), E)
+            else:
+                X = F._c(sep.embeddings.value(run))
+                xn = K.kmeans_normalize(X) if km.normalize_input else X
+            w = None
+            if km.latent_space_tensor is not None:
+                w = K.silence_weights(km.latent_space_tensor.value(run).reshape(xn.shape[0], xn.shape[1]).contiguous(), km.threshold)
+            return xn, w
+        for b0, n, ins in self._chunk_batches(mix, batch_size, 'embed_chunks'):
+            xn, w = self._eval_guarded({}, points, inputs=ins)
+            yield b0, n, xn, w
+
+    def embed_chunks(self, mix, batch_size=None):
+        """mix [C, L] -> (points [C, TF, E], weights [C, TF] or None): the separator's embeddings of every chunk as its k-means would
+        see them (normalised; the silence weights where the model was built --with_silence), in the batches of infer_chunks."""
+        pts = wts = None
+        for b0, n, xn, w in self._embed_batches(mix, batch_size):
+            if pts is None:
+                pts = torch.empty((mix.shape[0],) + tuple(xn.shape[1:]), dtype=xn.dtype, device=xn.device)
+                wts = None if w is None else torch.empty((mix.shape[0], xn.shape[1]), dtype=w.dtype, device=w.device)
+            pts[b0:b0 + n] = xn[:n]
+            if w is not None:
+                wts[b0:b0 + n] = w[:n]
+        return pts, wts
+
+    def infer_chunks_masked(self, mix, masks, batch_size=None):
+        """mix [C, L], masks [C, TF, S] -> est [C, S, L]: `output` for every chunk with the separator's `masks` node FED, in the batches of
+        infer_chunks.  Neither the embedding network nor the k-means runs; the enhance layer and the back end follow the masks."""
+        sep, _ = self._clustering_separator()
+        if not torch.is_tensor(masks) or masks.dim() != 3 or masks.shape[0] != mix.shape[0] or masks.shape[2] != self.S:
+            raise ValueError('infer_chunks_masked: masks [%d, TF, %d] for these chunks, got %s'
+                             % (mix.shape[0], self.S, tuple(masks.shape) if torch.is_tensor(masks) else type(masks).__name__))
+        est = None
+        for b0, n, ins in self._chunk_batches(mix, batch_size, 'infer_chunks_masked'):
+            mk = masks[b0:b0 + n]
+            B = ins[0][1].shape[0]
+            if n < B:
+                mk = torch.cat([mk, mk[-1:].expand(B - n, mk.shape[1], mk.shape[2])], dim=0)
+            out = self._eval_guarded({}, lambda run: self.output.value(run), inputs=ins + [(sep.masks, mk.contiguous())])
+            if est is None:
+                if tuple(out.shape) != (B, self.S, mix.shape[1]):
+                    raise ValueError('infer_chunks_masked: `output` is %s, expected [%d, %d, %d]: the model must return every sample of '
+                                     'a chunk' % (tuple(out.shape), B, self.S, mix.shape[1]))
+                est = torch.empty((mix.shape[0], self.S, mix.shape[1]), dtype=out.dtype, device=out.device)
+            est[b0:b0 + n] = out[:n]
+        return est
+
+    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes):
+        """mix [Ctot, L]: the chunks of R recordings, counts[r] each, one after the other -> est [Ctot, S, L] with ONE k-means per
+        recording over the embeddings of all its chunks.  2 ceil(Ctot / B) model passes whatever R is.  The points are held for a group
+        of consecutive recordings at a time (at most cap_bytes of them); the model passes run over the WHOLE stream in the same
+        batches whatever the groups are, and a recording is clustered on its own, so no result depends on the grouping."""
+        from ams_hip import kmeans_ragged as Kr
+        sep, km = self._clustering_separator()
+        cap = int(self.CLUSTER_CAP_BYTES if cap_bytes is None else cap_bytes)
+        counts = [int(c) for c in counts]
+        R, Ctot = len(counts), mix.shape[0]
+        first = np.concatenate([[0], np.cumsum(counts)])
+        labels = cents = bests = None
+        groups, g = None, 0                   # [(first recording, end recording)], the group being filled
+        pts = wts = None
+
+        def cluster(r0, r1):
+            TF, E = pts.shape[1], pts.shape[2]
+            seg = Kr.Segments([c * TF for c in counts[r0:r1]])
+            # seeds per recording, in list order: the caller's, or the model's own draw (reference / fast / keyed) over the recording's points
+            idx = np.concatenate([seeds[r] if seeds is not None else km._draw(km.nb_tries, counts[r] * TF).numpy() for r in range(r0, r1)])
+            c, lab, b = Kr.kmeans_ragged(pts.view(-1, E), seg, idx, km.nb_clusters, km.nb_tries, km.nb_iterations,
+                                         w=None if wts is None else wts.view(-1), assign_at_end=km.assign_at_end, normalize_input=False)
+            labels[first[r0]:first[r1]] = lab.view(-1, TF)
+            cents.append(c)
+            bests.append(b)
+
+        for b0, n, xn, w in self._embed_batches(mix, batch_size):
+            if groups is None:
+                TF, E = xn.shape[1], xn.shape[2]
+                Kr.check_domain(E, km.nb_clusters)
+                per_chunk = TF * E * 4
+                groups, r0, acc = [], 0, 0
+                for r, c in enumerate(counts):
+                    if c * per_chunk > cap:
+                        raise ValueError('recording %d: %d chunks of %d points x %d floats are %d bytes of embeddings, above the cap of %d '
+                                         'bytes (cluster_cap_bytes)' % (r, c, TF, E, c * per_chunk, cap))
+                    if acc + c * per_chunk > cap:
+                        groups.append((r0, r))
+                        r0, acc = r, 0
+                    acc += c * per_chunk
+                groups.append((r0, R))
+                labels = torch.empty((Ctot, TF), dtype=torch.int32, device=xn.device)
+                cents, bests = [], []
+            at = 0                           # rows of this batch handed out so far
+            while at < n:
+                r0, r1 = groups[g]
+                c0, c1 = int(first[r0]), int(first[r1])
+                if pts is None:
+                    pts = torch.empty((c1 - c0,) + tuple(xn.shape[1:]), dtype=xn.dtype, device=xn.device)
+                    wts = None if w is None else torch.empty((c1 - c0, xn.shape[1]), dtype=w.dtype, device=w.device)
+                k = min(n - at, c1 - (b0 + at))
+                pts[b0 + at - c0:b0 + at - c0 + k] = xn[at:at + k]
+                if w is not None:
+                    wts[b0 + at - c0:b0 + at - c0 + k] = w[at:at + k]
+                at += k
+                if b0 + at == c1:
+                    cluster(r0, r1)
+                    pts = wts = None
+                    g += 1
+        self.last_clustering = {'labels': labels, 'centroids': torch.cat(cents), 'best': torch.cat(bests), 'first_chunk': first,
+                                'groups': groups}
+        return self.infer_chunks_masked(mix, F.one_hot_masks(labels, self.S), batch_size)
+
+    def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
+                           cluster_cap_bytes=None):
         """x [N] (a tensor or anything numpy takes) -> out [S, N] on the device: chunks of the model's chunk_size, `hop` apart (default
         half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h).
+
+        clustering='recording' (DESIGN.md 4.10): ONE hard k-means over the embeddings of all chunks of the recording (TF points per chunk;
+        a frame in the overlap of two chunks is two points) instead of one per chunk, then the cross-fade with the identity track table:
+        no border statistics, no tracker.  kmeans_init_indices: [seeds [tries, clusters]] over the recording's C TF points (default: the
+        model's own draw); cluster_cap_bytes: see separate_recordings.  The default 'chunk' is the path described above, unchanged.
 
         fs: the sample rate of x (default config.fs, the rate the models work at).  At another rate -- or for int16 frames [N, CH], which
         are decoded and mixed down -- x is brought to config.fs on the device (ams_hip.resample, include/ams_resample.h), separated as
@@ -630,17 +816,23 @@ class Network(object):
         fs_in = config.fs if fs is None else int(fs)
         fs_out = fs_in if output_fs is None else int(output_fs)
         pcm = (x.dtype == torch.int16) if torch.is_tensor(x) else (getattr(x, 'dtype', None) == np.int16)
+        seeds = self._check_clustering(clustering, kmeans_init_indices, 1)
         if pcm or fs_in != config.fs or fs_out != config.fs:
-            return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out)
+            return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out, clustering, kmeans_init_indices, cluster_cap_bytes)
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
         if x.dim() != 1 or x.shape[0] < 1:
             raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
+        if clustering == 'recording':
+            mix = St.chunks(x, L, H)
+            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes)
+            trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(mix.shape[0], 1)       # the identity: nothing to track
+            return St.overlap_add(est, trk, x.shape[0], H)
         est = self.infer_chunks(St.chunks(x, L, H), batch_size)
         return St.stitch(est, x.shape[0], H)[0]
 
-    def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out):
+    def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out, clustering='chunk', kmeans_init_indices=None, cluster_cap_bytes=None):
         from ams_hip import resample as Rs
         Rs.ratio(fs_in, config.fs)                                 # a ValueError before anything is uploaded
         Rs.ratio(config.fs, fs_out)
@@ -654,14 +846,16 @@ class Network(object):
                              % (x.dtype, tuple(x.shape)))
         N = x.shape[0]
         x = Rs.from_pcm16(x, fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs)
-        out = self.separate_recording(x, hop=H, batch_size=batch_size)
+        out = self.separate_recording(x, hop=H, batch_size=batch_size, clustering=clustering, kmeans_init_indices=kmeans_init_indices,
+                                      cluster_cap_bytes=cluster_cap_bytes)
         if fs_out == config.fs:
             return out
         out = Rs.resample(out, config.fs, fs_out)
         n_out = -((-N * fs_out) // fs_in)                          # <= out.shape[1]: the way back yields ceil(M fs_out / config.fs)
         return out[:, :n_out].contiguous() if n_out < out.shape[1] else out
 
-    def separate_recordings(self, xs, hop=None, batch_size=None, fs=None, output_fs=None):
+    def separate_recordings(self, xs, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
+                            cluster_cap_bytes=None):
         """xs: a list of recordings, float32 [N_r] each (tensors or anything numpy takes) -> a list of [S, N_r] device tensors.  The chunks
         of ALL recordings go through infer_chunks as one stream -- ceil(Ctot / batch_size) model passes instead of one or more per
         recording -- and are cut, tracked and cross-faded by kernels whose launch count does not depend on len(xs)
@@ -672,7 +866,14 @@ class Network(object):
         bit-equal to separate_recording(xs[r]) -- except for a single recording, where the rows coincide.
 
         fs / output_fs as in separate_recording, for float32 [N_r] or int16 frames [N_r, CH] (all of one dtype): every recording goes
-        through the resampler on its own on the way in and out; the separation between is the batched one."""
+        through the resampler on its own on the way in and out; the separation between is the batched one.
+
+        clustering='recording' (DESIGN.md 4.10): one hard k-means per recording over the embeddings of all its chunks -- all recordings in
+        ONE ragged call (ams_hip.kmeans_ragged) between two sweeps of the chunk stream, 2 ceil(Ctot / batch_size) model passes -- and the
+        cross-fade with the identity track table.  kmeans_init_indices: one [tries, clusters] array per recording, over its C_r TF points
+        (default: the model's own draw, per recording in list order).  cluster_cap_bytes (default CLUSTER_CAP_BYTES = 8 GiB): the
+        embeddings are held for a group of consecutive recordings of at most that many bytes at a time; a recording's result does not
+        depend on the grouping; a single recording above the cap is refused."""
         from ams_hip import stitch as St
         from ams_hip import stitch_batch as Sb
         self._refuse_unless_separating()
@@ -681,6 +882,7 @@ class Network(object):
         xs = list(xs)
         if not xs:
             raise ValueError('separate_recordings: an empty list of recordings')
+        seeds = self._check_clustering(clustering, kmeans_init_indices, len(xs))
         L = int(self.args['chunk_size'])
         H = St.default_hop(L) if hop is None else int(hop)
         St.check_geometry(L, H)
@@ -719,7 +921,13 @@ class Network(object):
             for x, o, n in zip(xs, lay.x_off, lay.n):
                 host[o:o + n] = x.detach().cpu().numpy() if torch.is_tensor(x) else x
             mix = Sb.chunks_packed(torch.from_numpy(host).to(device), lay)
-        outs = [o for o, _, _ in Sb.stitch_many(self.infer_chunks(mix, batch_size), lay)]
+        if clustering == 'recording':
+            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes)
+            trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(lay.Ctot, 1)          # the identity: nothing to track
+            out = Sb.overlap_add_many(est, trk, lay)
+            outs = [out[int(o):int(o) + self.S * int(n)].view(self.S, int(n)) for o, n in zip(lay.out_off, lay.n)]
+        else:
+            outs = [o for o, _, _ in Sb.stitch_many(self.infer_chunks(mix, batch_size), lay)]
         if not resampled or fs_out == config.fs:
             return outs
         res = []
