@@ -19,11 +19,22 @@
 // row = (lane >> 4) + 4 * reg: with the matrix row on `col`, 16 lanes touch 16 consecutive doubles of a column.
 // A non-positive (or NaN) pivot sets info[m] once and writes NaN as the pivot; the NaN spreads through that matrix only.
 // No atomics, no persistent grid, every sum in a fixed order: a factor is a function of its matrix alone.
+//
+// Compiled a second time by bss_ragged.hip with AMS_BSS_RAGGED (libams_bss_ragged.so): that build keeps the Cholesky, the triangular
+// solves and block_sum and leaves out the exported entry points, the context and every use of hipFFT.  AMS_BSS_LAUNCH is
+// hipLaunchKernelGGL unless the including file counts its launches.
 #include <hip/hip_runtime.h>
+#ifndef AMS_BSS_RAGGED
 #include <hipfft/hipfft.h>
+#endif
 #include <math.h>
 #include <stdlib.h>
+#ifndef AMS_BSS_RAGGED
 #include "../../../include/ams_bss_batch.h"
+#endif
+#ifndef AMS_BSS_LAUNCH
+#define AMS_BSS_LAUNCH hipLaunchKernelGGL
+#endif
 
 namespace {
 
@@ -36,13 +47,16 @@ constexpr int MAXGRID = 65535;
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
+#ifndef AMS_BSS_RAGGED
 struct plan_set {
     int nutt;                      // 0: not planned
     hipfftHandle fwd_in, inv_corr, fwd_c, inv_proj;
 };
+#endif
 
 }  // namespace
 
+#ifndef AMS_BSS_RAGGED
 struct ams_bssb_ctx {
     int U, K, S, L, F, n, nc, Lp, NP, KS;
     plan_set full, part;           // plans for nutt == max_utt, and for the last other nutt asked for
@@ -50,9 +64,11 @@ struct ams_bssb_ctx {
     // offsets (in bytes) into the caller's workspace; `a` holds xs, then cpad, then pspec; `b` holds corr, then cspec, then proj
     size_t o_tpad, o_spec, o_a, o_b, o_G, o_Gj, o_Df, o_Dj, o_part, o_info;
 };
+#endif
 
 namespace {
 
+#ifndef AMS_BSS_RAGGED
 // ---------------------------------------------------------------- assembly and reduction kernels, blockIdx.z = utterance
 // rows of an utterance: [0, S) references, [S, S + K*S) estimates (set-major)
 __global__ void pad_kernel(const double* __restrict__ ref, const double* __restrict__ est, double* __restrict__ tpad, int S, int KS,
@@ -160,6 +176,7 @@ __global__ void prod_kernel(const hipfftDoubleComplex* __restrict__ spec_, const
         pspec[k] = acc;
     }
 }
+#endif
 
 __device__ __forceinline__ double block_sum(double v, double* sm) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
@@ -172,6 +189,7 @@ __device__ __forceinline__ double block_sum(double v, double* sm) {
     return t;
 }
 
+#ifndef AMS_BSS_RAGGED
 // as sums_kernel of bss_eval.hip; blockIdx.y = ke * S + j, blockIdx.z = utterance
 __global__ __launch_bounds__(256) void sums_kernel(const double* __restrict__ tpad_, const double* __restrict__ proj_,
                                                    double* __restrict__ part_, int S, int KS, int n, int Lp) {
@@ -226,6 +244,7 @@ __global__ void crit_kernel(const double* __restrict__ part_, const int* __restr
     out[2 * S * S + ej] = bad ? nanv : 10.0 * log10(s[3] / (s[4] + 1e-12));
     if (pair == 0) info_out[u] = bad;
 }
+#endif
 
 // ---------------------------------------------------------------- batched blocked Cholesky
 // Diagonal block [k0, k0 + nb) of every matrix, in LDS.  s[col][row]; a short last block is padded with the identity.
@@ -345,12 +364,12 @@ int potrf_batched(double* A, int n, int lda, long stride, int nmat, int* info, h
     if (hipMemsetAsync(info, 0, (size_t)nmat * sizeof(int), st) != hipSuccess) return -3;
     const int gm = nmat < MAXGRID ? nmat : MAXGRID;
     for (int k0 = 0; k0 < n; k0 += NB) {
-        hipLaunchKernelGGL(potrf_diag_kernel, dim3(gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0, info);
+        AMS_BSS_LAUNCH(potrf_diag_kernel, dim3(gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0, info);
         const int rem = n - k0 - NB;
         if (rem <= 0) break;
         const int T = (rem + TM - 1) / TM;
-        hipLaunchKernelGGL(potrf_panel_kernel, dim3(T, gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0);
-        hipLaunchKernelGGL(potrf_trail_kernel, dim3(T, T, gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0);
+        AMS_BSS_LAUNCH(potrf_panel_kernel, dim3(T, gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0);
+        AMS_BSS_LAUNCH(potrf_trail_kernel, dim3(T, T, gm), dim3(256), 0, st, A, n, lda, stride, nmat, k0);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -444,13 +463,14 @@ __global__ __launch_bounds__(256) void solve_bwd_kernel(const double* __restrict
 
 void solve_batched(const double* Lf, int n, int lda, long strideL, double* B, int ldb, long strideB, int R, int nmat, hipStream_t st) {
     const dim3 grid((R + RC - 1) / RC, nmat < MAXGRID ? nmat : MAXGRID);
-    hipLaunchKernelGGL(solve_fwd_kernel, grid, dim3(256), 0, st, Lf, n, lda, strideL, B, ldb, strideB, R, nmat);
-    hipLaunchKernelGGL(solve_bwd_kernel, grid, dim3(256), 0, st, Lf, n, lda, strideL, B, ldb, strideB, R, nmat);
+    AMS_BSS_LAUNCH(solve_fwd_kernel, grid, dim3(256), 0, st, Lf, n, lda, strideL, B, ldb, strideB, R, nmat);
+    AMS_BSS_LAUNCH(solve_bwd_kernel, grid, dim3(256), 0, st, Lf, n, lda, strideL, B, ldb, strideB, R, nmat);
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
+#ifndef AMS_BSS_RAGGED
 void destroy_plans(plan_set* p) {
     if (!p->nutt) return;
     hipfftDestroy(p->fwd_in); hipfftDestroy(p->inv_corr); hipfftDestroy(p->fwd_c); hipfftDestroy(p->inv_proj);
@@ -478,9 +498,11 @@ bool make_plans(const ams_bssb_ctx* c, plan_set* p, int nutt) {
     p->nutt = nutt;
     return true;
 }
+#endif
 
 }  // namespace
 
+#ifndef AMS_BSS_RAGGED
 extern "C" {
 
 int ams_bssb_abi_version(void) { return 1; }
@@ -581,3 +603,4 @@ int ams_bssb_eval(ams_bssb_ctx* c, int nutt, const double* ref, const double* es
 }
 
 }  // extern "C"
+#endif

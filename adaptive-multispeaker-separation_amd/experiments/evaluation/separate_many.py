@@ -10,7 +10,15 @@ D/<stem>_<k>.wav (.npy for an .npy input), k = 0 .. nb_speakers - 1, where <stem
 two inputs with one stem are refused.
 
 With --resample the inputs are 16-bit PCM .wav files of 1 .. 8 channels at any common rate (they may differ from file to file: the
-files of one rate are separated together); the outputs come back at --output_rate (default: the rate of their input)."""
+files of one rate are separated together); the outputs come back at --output_rate (default: the rate of their input).
+
+With --reference_dir R the separated tracks are scored against the true sources R/<stem>_<k>.wav (.npy for an .npy input), each of
+the input's length: ONE ragged BSS-eval call over all recordings (utils.bss_eval.bss_eval_sources_ragged) with two sets
+of estimates per recording -- the mixture repeated nb_speakers times (the "no separation" line of eval.py) and the tracks as they were
+written -- and D/scores.json holds the criteria per recording, their means and the mean improvement over the mixture.
+--score_both_clusterings separates under both clusterings, writes the tracks of the one --clustering names and scores both as a third
+set of the same call.  Scoring is at the model's rate only: --reference_dir with --resample is refused."""
+import json
 import os
 import wave
 
@@ -38,9 +46,74 @@ def build_parser():
     p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
                           "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
                           "(hard k-means only; DESIGN.md 4.10)")
+    p.parser.add_argument('--reference_dir', help='Score the separated tracks against the true sources <reference_dir>/<stem>_<k>.wav '
+                          '(.npy for an .npy input) and write <output_dir>/scores.json (DESIGN.md 6c)', required=False, default=None)
+    p.parser.add_argument('--score_both_clusterings', action='store_true', help="With --reference_dir: separate under 'chunk' and "
+                          "under 'recording', write the tracks of the one --clustering names, score both in the same call")
     p.add_adapt_args()
     p.add_separator_args()
     return p
+
+
+def read_references(paths, recs, reference_dir, nsrc):
+    """[float32 [S, N]] per input: <reference_dir>/<stem>_<k>, k = 0 .. S - 1, each of the input's length; anything else is refused with
+    the file named."""
+    refs = []
+    for p, (x, _) in zip(paths, recs):
+        stem, ext = os.path.splitext(os.path.basename(p))
+        rows = []
+        for k in range(nsrc):
+            rp = os.path.join(reference_dir, '%s_%d%s' % (stem, k, '.npy' if ext == '.npy' else '.wav'))
+            if not os.path.isfile(rp):
+                raise SystemExit('%s: the true source %d of %s is missing' % (rp, k, p))
+            r = one.read_input(rp)
+            if r.shape[0] != x.shape[0]:
+                raise SystemExit('%s has %d samples, %s has %d: a true source has the length of its mixture' % (rp, r.shape[0], p, x.shape[0]))
+            rows.append(r)
+        refs.append(np.stack(rows))
+    return refs
+
+
+def as_written(out, as_npy):
+    """The tracks as write_outputs stores them and read_input reads them back: float32, through 16-bit PCM for a .wav."""
+    out = np.asarray(out)
+    if as_npy:
+        return np.asarray(out, np.float32)
+    if not np.all(np.isfinite(out)):
+        raise SystemExit('%d of %d separated samples are not finite; nothing scored' % (int((~np.isfinite(out)).sum()), out.size))
+    pcm = np.clip(np.rint(np.asarray(out, np.float64) * 32768.0), -32767, 32767).astype('<i2')
+    return pcm.astype(np.float32) / np.float32(32768.0)
+
+
+def score(paths, recs, refs, sets):
+    """sets: [(name, [tracks [S, N] per recording])] -> the dictionary of scores.json.  ONE ragged call: per recording the mixture
+    repeated S times, then every set."""
+    from utils.bss_eval import bss_eval_pairs_ragged, _select_permutation
+    S = refs[0].shape[0]
+    names = ['mixture'] + [n for n, _ in sets]
+    ests = []
+    for i, (x, _) in enumerate(recs):
+        ests.append(np.stack([np.repeat(np.asarray(x, np.float32)[None], S, axis=0)] + [t[i] for _, t in sets]))
+    crit, info = bss_eval_pairs_ragged(refs, ests)
+    num = lambda v: [None if not np.isfinite(a) else float(a) for a in v]       # noqa: E731
+    per, good = [], []
+    for i, p in enumerate(paths):
+        entry = {'input': p, 'samples': int(refs[i].shape[1]), 'info': int(info[i]), 'sets': {}}
+        vals = np.empty((len(names), 3, S))
+        for k, name in enumerate(names):
+            sdr, sir, sar, perm = _select_permutation(crit[i, k, 0], crit[i, k, 1], crit[i, k, 2])
+            vals[k] = sdr, sir, sar
+            entry['sets'][name] = {'sdr': num(sdr), 'sir': num(sir), 'sar': num(sar), 'perm': [int(v) for v in perm]}
+        per.append(entry)
+        if info[i] == 0:
+            good.append(vals)
+    res = {'flen': 512, 'sets': names, 'recordings': per, 'scored': len(good), 'means': None, 'improvement': None}
+    if good:
+        m = np.mean(np.stack(good), axis=(0, 3))                               # [set, criterion]
+        crits = ('sdr', 'sir', 'sar')
+        res['means'] = {n: {c: float(m[k, j]) for j, c in enumerate(crits)} for k, n in enumerate(names)}
+        res['improvement'] = {n: {c: float(m[k, j] - m[0, j]) for j, c in enumerate(crits)} for k, n in enumerate(names) if k}
+    return res
 
 
 def input_paths(args):
@@ -95,8 +168,13 @@ def main(argv=None):
                          'without them' % args.sortofmodel)
     if args.output_rate is not None and not args.resample:
         raise SystemExit('--output_rate goes with --resample')
+    if args.score_both_clusterings and args.reference_dir is None:
+        raise SystemExit('--score_both_clusterings goes with --reference_dir')
+    if args.reference_dir is not None and args.resample:
+        raise SystemExit('--reference_dir with --resample: scoring at a rate other than the model\'s %d Hz is not built' % config.fs)
     paths = input_paths(args)
     recs = read_all(paths, args.resample)
+    refs = None if args.reference_dir is None else read_references(paths, recs, args.reference_dir, args.nb_speakers)
     if args.resample:
         from ams_hip import resample
         for p, (_, fs) in zip(paths, recs):
@@ -110,8 +188,17 @@ def main(argv=None):
     tr = inferencer(sep, 'inference', **vars(args))
     model = tr.prepare_inference()
     outs = [None] * len(paths)
+    other = None
     with tr.graph.as_default():
-        if args.resample:
+        if args.score_both_clusterings:
+            # a soft k-means model is refused here, with the message clustering='recording' gives, before anything is separated; the
+            # clustering whose tracks are written runs first, so that it draws the k-means seeds it draws without scoring
+            model._check_clustering('recording', None, len(recs))
+            mode = 'recording' if args.clustering == 'chunk' else 'chunk'
+            xs = [x for x, _ in recs]
+            outs = [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=args.clustering)]
+            other = (mode, [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=mode)])
+        elif args.resample:
             for fs in sorted(set(fs for _, fs in recs)):          # the files of one rate together
                 idx = [i for i, (_, f) in enumerate(recs) if f == fs]
                 res = model.separate_recordings([recs[i][0] for i in idx], hop=args.hop, fs=fs, output_fs=args.output_rate,
@@ -126,6 +213,17 @@ def main(argv=None):
         stem = os.path.splitext(os.path.basename(p))[0]
         out_fs = (fs if args.output_rate is None else args.output_rate) if args.resample else None
         written += one.write_outputs(os.path.join(args.output_dir, stem), out, p.endswith('.npy'), out_fs)
+    if refs is not None:
+        npy = [p.endswith('.npy') for p in paths]
+        sets = [(args.clustering if other else 'separated', [as_written(o, n) for o, n in zip(outs, npy)])]
+        if other:
+            sets.append((other[0], [as_written(o, n) for o, n in zip(other[1], npy)]))
+            sets.sort(key=lambda s: ('chunk', 'recording').index(s[0]))
+        scores = score(paths, recs, refs, sets)
+        sp = os.path.join(args.output_dir, 'scores.json')
+        with open(sp, 'w') as f:
+            json.dump(scores, f, indent=1)
+        written.append(sp)
     print('\n'.join(written))
     return written
 
