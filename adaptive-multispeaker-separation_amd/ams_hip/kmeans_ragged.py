@@ -152,10 +152,8 @@ def check_seeds(init_idx, seg, tries, C):
     return np.ascontiguousarray(idx, dtype=np.int32)
 
 
-def kmeans_ragged(x, p_off, init_idx, C, tries, iterations, w=None, assign_at_end=True, normalize_input=True, want_inertia=False):
-    """x [Ptot, E] float32 on the device, p_off: a Segments or the sizes P_r, init_idx: HOST integers [R tries, C] relative to each segment
-    (they are drawn on the host anyway), w [Ptot] or None -> (centroids [R, C, E], labels int32 [Ptot], best int32 [R]) (and
-    inertia [R tries] with want_inertia).  iterations + 4 launches after the normalisation, no host synchronisation."""
+def _every_try(x, p_off, init_idx, C, tries, iterations, w, normalize_input):
+    """The checks and the init, iterate and inertia launches of kmeans_ragged -> (xn, seg, centroids [R tries, C, E], inertia [R tries])."""
     C, tries, iterations = int(C), int(tries), int(iterations)
     seg = segments(p_off)
     if tries < 1 or iterations < 0:
@@ -193,10 +191,45 @@ def kmeans_ragged(x, p_off, init_idx, C, tries, iterations, w=None, assign_at_en
     inertia = torch.empty(RT, dtype=torch.float32, device=dev)
     _launch(lib.ams_kmr_inertia(_p(xn), _p(w), *tabs, _p(cent), _p(inertia), R, tries, seg.Gtot, seg.Pmax, E, C, _p(ws), nb, _p(tk), _s()),
             'ams_kmr_inertia')
+    return xn, seg, cent, inertia
+
+
+def kmeans_ragged_tries(x, p_off, init_idx, C, tries, iterations, w=None, normalize_input=True):
+    """The arguments of kmeans_ragged -> (centroids [R tries, C, E], inertia [R tries]) of EVERY try: the run without its select and
+    labels launches (iterations + 2 launches), for a caller that picks the try itself (ams_hip/spk_count.py)."""
+    return _every_try(x, p_off, init_idx, C, tries, iterations, w, normalize_input)[2:]
+
+
+def labels_ragged(xn, p_off, centroids, w=None, out=None):
+    """The labels launch alone: xn [Ptot, E] ALREADY normalised, centroids [R, C, E] (one set per segment), w as ams_kmr_labels takes it
+    (None: the assign_at_end re-assignment; the run's weights otherwise) -> labels int32 [Ptot] (written to `out` if given)."""
+    seg = segments(p_off)
+    if not torch.is_tensor(xn) or xn.dim() != 2 or xn.shape[0] != seg.Ptot:
+        raise ValueError('ragged k-means: the points are a [Ptot, E] = [%d, E] tensor' % seg.Ptot)
+    E = int(xn.shape[1])
+    if not torch.is_tensor(centroids) or centroids.dim() != 3 or centroids.shape[0] != seg.R or centroids.shape[2] != E:
+        raise ValueError('ragged k-means: the centroids are a [R, C, E] = [%d, C, %d] tensor' % (seg.R, E))
+    C = int(centroids.shape[1])
+    check_domain(E, C)
+    if w is not None and (not torch.is_tensor(w) or tuple(w.shape) != (seg.Ptot,)):
+        raise ValueError('ragged k-means: the weights are a [Ptot] = [%d] tensor' % seg.Ptot)
+    ops._chk(xn, w, centroids)
+    t = seg.tables(xn.device)
+    labels = torch.empty(seg.Ptot, dtype=torch.int32, device=xn.device) if out is None else out
+    _launch(load().ams_kmr_labels(_p(xn), _p(w), _p(t['tab']), _p(t['p_off']), _p(t['g_off']), _p(centroids), _p(labels), seg.R, seg.Gtot, E, C,
+                                  _s()), 'ams_kmr_labels')
+    return labels
+
+
+def kmeans_ragged(x, p_off, init_idx, C, tries, iterations, w=None, assign_at_end=True, normalize_input=True, want_inertia=False):
+    """x [Ptot, E] float32 on the device, p_off: a Segments or the sizes P_r, init_idx: HOST integers [R tries, C] relative to each segment
+    (they are drawn on the host anyway), w [Ptot] or None -> (centroids [R, C, E], labels int32 [Ptot], best int32 [R]) (and
+    inertia [R tries] with want_inertia).  iterations + 4 launches after the normalisation, no host synchronisation."""
+    xn, seg, cent, inertia = _every_try(x, p_off, init_idx, C, tries, iterations, w, normalize_input)
+    C, tries, R, E, dev = int(C), int(tries), seg.R, int(x.shape[1]), x.device
     best = torch.empty(R, dtype=torch.int32, device=dev)
     sel = torch.empty((R, C, E), dtype=torch.float32, device=dev)
-    _launch(lib.ams_kmr_select(_p(inertia), _p(cent), _p(best), _p(sel), R, tries, E, C, _s()), 'ams_kmr_select')
-    labels = torch.empty(seg.Ptot, dtype=torch.int32, device=dev)
+    _launch(load().ams_kmr_select(_p(inertia), _p(cent), _p(best), _p(sel), R, tries, E, C, _s()), 'ams_kmr_select')
     # at the end: re-assigned without the silence weights (the reference's assign_at_end); else the chosen try's own last assignment
-    _launch(lib.ams_kmr_labels(_p(xn), _p(None if assign_at_end else w), *tabs, _p(sel), _p(labels), R, seg.Gtot, E, C, _s()), 'ams_kmr_labels')
+    labels = labels_ragged(xn, seg, sel, None if assign_at_end else w)
     return (sel, labels, best, inertia) if want_inertia else (sel, labels, best)

@@ -7,6 +7,10 @@ of --chunk_size samples, the chunk outputs tracked across the chunk borders and 
 ams_hip/stitch.py).  Input: 16-bit PCM mono .wav at config.fs, or .npy float32 [N].  Output: <prefix>_<k>.wav (or .npy for an .npy
 input), k = 0 .. nb_speakers - 1.  Without --resample there is no resampling and no channel mixing: anything else is refused.
 
+With --clustering recording, --speakers auto (2 .. nb_speakers) or --speakers LO:HI chooses the number of speakers S_r of the recording
+ and k = 0 .. S_r - 1 are written; LO = 1 needs --min_score X, the score below which the recording counts as one
+speaker.
+
 With --resample the input may be a 16-bit PCM .wav of 1 .. 8 channels at any rate whose reduced ratio to config.fs has both terms in
 1 .. 1024 (every standard rate from 11025 to 96000 Hz), or an .npy float32 [N] at --input_rate.  The frames are uploaded as they are;
 decoding, the channel down-mix and the way to config.fs are one GPU kernel, the separated tracks go back to --output_rate (default: the
@@ -38,9 +42,37 @@ def build_parser():
     p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
                           "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
                           "(hard k-means only; DESIGN.md 4.10)")
+    add_speakers_args(p.parser)
     p.add_adapt_args()
     p.add_separator_args()
     return p
+
+
+def add_speakers_args(parser):
+    parser.add_argument('--speakers', help="With --clustering recording: choose every recording's number of speakers, 'auto' "
+                        "(2 .. nb_speakers) or LO:HI (DESIGN.md 4.11); the tracks 0 .. S_r - 1 are written", required=False, default=None)
+    parser.add_argument('--min_score', type=float, help='With --speakers 1:HI: the score below which a recording counts as one speaker '
+                        '(no default: the criterion has not been measured on a trained model)', required=False, default=None)
+
+
+def speakers_arg(args):
+    """--speakers / --min_score -> None or (lo, hi), refused with SystemExit before a model is built."""
+    if args.speakers is None:
+        if args.min_score is not None:
+            raise SystemExit('--min_score goes with --speakers')
+        return None
+    from ams_hip import spk_count
+    if args.clustering != 'recording':
+        raise SystemExit('--speakers goes with --clustering recording: the count is chosen on the embeddings of a whole recording')
+    if 'enhance' in args.sortofmodel:
+        raise SystemExit('--speakers with --sortofmodel %s: choosing the count for a model with an enhance layer is not built'
+                         % args.sortofmodel)
+    try:
+        lo, hi = spk_count.parse_speakers(args.speakers, args.nb_speakers)
+        spk_count.check_range(lo, hi, args.nb_speakers, args.min_score)
+    except ValueError as e:
+        raise SystemExit('--speakers %s: %s' % (args.speakers, e))
+    return lo, hi
 
 
 def read_wav(path, fs=None):
@@ -109,6 +141,7 @@ def main(argv=None):
     if 'pretraining' in args.sortofmodel:
         raise SystemExit('--sortofmodel %s: a pretraining model separates with masks made from the clean sources; a recording comes '
                          'without them' % args.sortofmodel)
+    speakers = speakers_arg(args)
     fs = out_fs = None
     if args.resample:
         from ams_hip import resample
@@ -137,7 +170,8 @@ def main(argv=None):
     tr = inferencer(sep, 'inference', **vars(args))
     model = tr.prepare_inference()
     with tr.graph.as_default():
-        out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs, clustering=args.clustering).cpu().numpy()
+        out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs, clustering=args.clustering, speakers=speakers,
+                                       min_score=args.min_score).cpu().numpy()
     paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'), out_fs)
     print('\n'.join(paths))
     return paths

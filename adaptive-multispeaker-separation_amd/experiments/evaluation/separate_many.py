@@ -17,7 +17,11 @@ the input's length: ONE ragged BSS-eval call over all recordings (utils.bss_eval
 of estimates per recording -- the mixture repeated nb_speakers times (the "no separation" line of eval.py) and the tracks as they were
 written -- and D/scores.json holds the criteria per recording, their means and the mean improvement over the mixture.
 --score_both_clusterings separates under both clusterings, writes the tracks of the one --clustering names and scores both as a third
-set of the same call.  Scoring is at the model's rate only: --reference_dir with --resample is refused."""
+set of the same call.  Scoring is at the model's rate only: --reference_dir with --resample is refused.
+
+With --clustering recording, --speakers auto|LO:HI (and --min_score X for LO = 1) chooses every recording's number of speakers S_r
+(DESIGN.md 4.11): D/<stem>_0 .. D/<stem>_{S_r - 1} are written, and D/counts.json holds every stem's count and the scores of its
+candidate counts.  Scoring recordings of differing numbers of tracks is not built: --speakers with --reference_dir is refused."""
 import json
 import os
 import wave
@@ -50,6 +54,7 @@ def build_parser():
                           '(.npy for an .npy input) and write <output_dir>/scores.json (DESIGN.md 6c)', required=False, default=None)
     p.parser.add_argument('--score_both_clusterings', action='store_true', help="With --reference_dir: separate under 'chunk' and "
                           "under 'recording', write the tracks of the one --clustering names, score both in the same call")
+    one.add_speakers_args(p.parser)
     p.add_adapt_args()
     p.add_separator_args()
     return p
@@ -172,6 +177,9 @@ def main(argv=None):
         raise SystemExit('--score_both_clusterings goes with --reference_dir')
     if args.reference_dir is not None and args.resample:
         raise SystemExit('--reference_dir with --resample: scoring at a rate other than the model\'s %d Hz is not built' % config.fs)
+    if args.speakers is not None and args.reference_dir is not None:
+        raise SystemExit('--speakers with --reference_dir: scoring recordings of differing numbers of tracks is not built')
+    speakers = one.speakers_arg(args)
     paths = input_paths(args)
     recs = read_all(paths, args.resample)
     refs = None if args.reference_dir is None else read_references(paths, recs, args.reference_dir, args.nb_speakers)
@@ -189,6 +197,14 @@ def main(argv=None):
     model = tr.prepare_inference()
     outs = [None] * len(paths)
     other = None
+    counted = [None] * len(paths)                                 # with --speakers: (count, scores of the candidate counts) per input
+    spk = dict(speakers=speakers, min_score=args.min_score)
+
+    def note(idx):
+        if speakers is not None:
+            lc = model.last_clustering
+            for i, c, sc in zip(idx, lc['counts'].tolist(), lc['scores'].tolist()):
+                counted[i] = (int(c), sc)
     with tr.graph.as_default():
         if args.score_both_clusterings:
             # a soft k-means model is refused here, with the message clustering='recording' gives, before anything is separated; the
@@ -202,17 +218,30 @@ def main(argv=None):
             for fs in sorted(set(fs for _, fs in recs)):          # the files of one rate together
                 idx = [i for i, (_, f) in enumerate(recs) if f == fs]
                 res = model.separate_recordings([recs[i][0] for i in idx], hop=args.hop, fs=fs, output_fs=args.output_rate,
-                                                clustering=args.clustering)
+                                                clustering=args.clustering, **spk)
+                note(idx)
                 for i, o in zip(idx, res):
                     outs[i] = o.cpu().numpy()
         else:
-            outs = [o.cpu().numpy() for o in model.separate_recordings([x for x, _ in recs], hop=args.hop, clustering=args.clustering)]
+            outs = [o.cpu().numpy() for o in model.separate_recordings([x for x, _ in recs], hop=args.hop, clustering=args.clustering,
+                                                                       **spk)]
+            note(range(len(paths)))
     os.makedirs(args.output_dir, exist_ok=True)
     written = []
     for p, (_, fs), out in zip(paths, recs, outs):
         stem = os.path.splitext(os.path.basename(p))[0]
         out_fs = (fs if args.output_rate is None else args.output_rate) if args.resample else None
         written += one.write_outputs(os.path.join(args.output_dir, stem), out, p.endswith('.npy'), out_fs)
+    if speakers is not None:
+        lo, hi = speakers
+        num = lambda v: None if not np.isfinite(v) else float(v)               # noqa: E731  (a disqualified candidate: -inf -> null)
+        cj = {'speakers': [lo, hi], 'min_score': args.min_score, 'candidates': list(range(max(lo, 2), hi + 1)), 'recordings': {}}
+        for p, (c, sc) in zip(paths, counted):
+            cj['recordings'][os.path.splitext(os.path.basename(p))[0]] = {'count': c, 'scores': [num(v) for v in sc]}
+        cp = os.path.join(args.output_dir, 'counts.json')
+        with open(cp, 'w') as f:
+            json.dump(cj, f, indent=1)
+        written.append(cp)
     if refs is not None:
         npy = [p.endswith('.npy') for p in paths]
         sets = [(args.clustering if other else 'separated', [as_written(o, n) for o, n in zip(outs, npy)])]

@@ -627,6 +627,28 @@ class Network(object):
             raise ValueError("clustering='recording' needs a model with a k-means separator (`separate` on embeddings); this one has none")
         return sep, km
 
+    def _check_speakers(self, clustering, speakers, min_score):
+        """The refusals of `speakers`, all before anything is uploaded.  Returns None (the model's fixed S) or
+        (lo, hi, min_score)."""
+        if speakers is None:
+            if min_score is not None:
+                raise ValueError("min_score belongs to speakers='auto' or (lo, hi); without `speakers` every recording has the model's %d"
+                                 % self.S)
+            return None
+        from ams_hip import spk_count as Sc
+        lo, hi = Sc.parse_speakers(speakers, self.S)
+        if clustering != 'recording':
+            raise ValueError("speakers=%r needs clustering='recording': the count is chosen on the embeddings of a whole recording"
+                             % (speakers,))
+        sep, km = self._clustering_separator()
+        if km.beta is not None:
+            raise ValueError("speakers=%r is hard assignment only: this model runs a soft k-means (beta_kmeans = %r)" % (speakers, km.beta))
+        if hasattr(sep, '_cache_enhance'):
+            raise ValueError("speakers=%r with an enhance layer is not built: its softmax over the %d tracks would put energy into the "
+                             "tracks a recording of fewer speakers leaves empty" % (speakers, self.S))
+        Sc.check_range(lo, hi, self.S, min_score, getattr(sep, 'embedding_size', None))
+        return lo, hi, None if min_score is None else float(min_score)
+
     def _check_clustering(self, clustering, kmeans_init_indices, R):
         """The refusals of the clustering arguments, all before anything is uploaded.  Returns the seeds as a list of R int32 [tries, C]
         host arrays (None: to be drawn)."""
@@ -731,18 +753,22 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
-    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes):
+    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes, speakers=None):
         """mix [Ctot, L]: the chunks of R recordings, counts[r] each, one after the other -> est [Ctot, S, L] with ONE k-means per
         recording over the embeddings of all its chunks.  2 ceil(Ctot / B) model passes whatever R is.  The points are held for a group
         of consecutive recordings at a time (at most cap_bytes of them); the model passes run over the WHOLE stream in the same
-        batches whatever the groups are, and a recording is clustered on its own, so no result depends on the grouping."""
+        batches whatever the groups are, and a recording is clustered on its own, so no result depends on the grouping.
+        speakers = (lo, hi, min_score): every recording's number of clusters is chosen in lo .. hi (ams_hip/spk_count.py, DESIGN.md
+        4.11); labels below the recording's count leave the other mask columns all-zero."""
         from ams_hip import kmeans_ragged as Kr
+        from ams_hip import spk_count as Sc
         sep, km = self._clustering_separator()
         cap = int(self.CLUSTER_CAP_BYTES if cap_bytes is None else cap_bytes)
         counts = [int(c) for c in counts]
         R, Ctot = len(counts), mix.shape[0]
         first = np.concatenate([[0], np.cumsum(counts)])
         labels = cents = bests = None
+        counted = {'counts': [], 'scores': [], 'tries': []}
         groups, g = None, 0                   # [(first recording, end recording)], the group being filled
         pts = wts = None
 
@@ -751,6 +777,19 @@ class Network(object):
             seg = Kr.Segments([c * TF for c in counts[r0:r1]])
             # seeds per recording, in list order: the caller's, or the model's own draw (reference / fast / keyed) over the recording's points
             idx = np.concatenate([seeds[r] if seeds is not None else km._draw(km.nb_tries, counts[r] * TF).numpy() for r in range(r0, r1)])
+            if speakers is not None:
+                lo, hi, min_score = speakers
+                res = Sc.count_clusters(pts.view(-1, E), seg, idx, lo, hi, km.nb_tries, km.nb_iterations,
+                                        w=None if wts is None else wts.view(-1), assign_at_end=km.assign_at_end, normalize_input=False,
+                                        min_score=min_score)
+                labels[first[r0]:first[r1]] = res['labels'].view(-1, TF)
+                cents.append(res['centroids'])
+                # the chosen try of the chosen candidate (-1 for a recording of one speaker)
+                cd = res['cand'].long()
+                bests.append(torch.where(cd >= 0, res['tries'].gather(1, cd.clamp(min=0)[:, None])[:, 0], cd.to(torch.int32)))
+                for key, name in (('counts', 'count'), ('scores', 'scores'), ('tries', 'tries')):
+                    counted[key].append(res[name])
+                return
             c, lab, b = Kr.kmeans_ragged(pts.view(-1, E), seg, idx, km.nb_clusters, km.nb_tries, km.nb_iterations,
                                          w=None if wts is None else wts.view(-1), assign_at_end=km.assign_at_end, normalize_input=False)
             labels[first[r0]:first[r1]] = lab.view(-1, TF)
@@ -760,7 +799,10 @@ class Network(object):
         for b0, n, xn, w in self._embed_batches(mix, batch_size):
             if groups is None:
                 TF, E = xn.shape[1], xn.shape[2]
-                Kr.check_domain(E, km.nb_clusters)
+                if speakers is None:
+                    Kr.check_domain(E, km.nb_clusters)
+                else:
+                    Sc.check_range(speakers[0], speakers[1], self.S, speakers[2], E)
                 per_chunk = TF * E * 4
                 groups, r0, acc = [], 0, 0
                 for r, c in enumerate(counts):
@@ -792,10 +834,12 @@ class Network(object):
                     g += 1
         self.last_clustering = {'labels': labels, 'centroids': torch.cat(cents), 'best': torch.cat(bests), 'first_chunk': first,
                                 'groups': groups}
+        if speakers is not None:
+            self.last_clustering.update({k: torch.cat(v) for k, v in counted.items()})
         return self.infer_chunks_masked(mix, F.one_hot_masks(labels, self.S), batch_size)
 
     def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
-                           cluster_cap_bytes=None):
+                           cluster_cap_bytes=None, speakers=None, min_score=None):
         """x [N] (a tensor or anything numpy takes) -> out [S, N] on the device: chunks of the model's chunk_size, `hop` apart (default
         half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h).
 
@@ -803,6 +847,11 @@ class Network(object):
         a frame in the overlap of two chunks is two points) instead of one per chunk, then the cross-fade with the identity track table:
         no border statistics, no tracker.  kmeans_init_indices: [seeds [tries, clusters]] over the recording's C TF points (default: the
         model's own draw); cluster_cap_bytes: see separate_recordings.  The default 'chunk' is the path described above, unchanged.
+
+        speakers='auto' (= (2, S)) or (lo, hi), with clustering='recording' (DESIGN.md 4.11): the number of speakers S_r of the recording
+        is chosen in lo .. hi by the simplified silhouette of the k-means of every candidate count, and out is [S_r, N], the first S_r
+        tracks.  lo == 1 needs min_score: the score below which the recording counts as one speaker.  last_clustering then also
+        holds 'counts', 'scores' and 'tries'.  How well the criterion counts speakers on a trained model has not been measured.
 
         fs: the sample rate of x (default config.fs, the rate the models work at).  At another rate -- or for int16 frames [N, CH], which
         are decoded and mixed down -- x is brought to config.fs on the device (ams_hip.resample, include/ams_resample.h), separated as
@@ -817,8 +866,10 @@ class Network(object):
         fs_out = fs_in if output_fs is None else int(output_fs)
         pcm = (x.dtype == torch.int16) if torch.is_tensor(x) else (getattr(x, 'dtype', None) == np.int16)
         seeds = self._check_clustering(clustering, kmeans_init_indices, 1)
+        spk = self._check_speakers(clustering, speakers, min_score)
         if pcm or fs_in != config.fs or fs_out != config.fs:
-            return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out, clustering, kmeans_init_indices, cluster_cap_bytes)
+            return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out, clustering, kmeans_init_indices, cluster_cap_bytes,
+                                            speakers, min_score)
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
@@ -826,13 +877,15 @@ class Network(object):
             raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
         if clustering == 'recording':
             mix = St.chunks(x, L, H)
-            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes)
+            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes, spk)
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(mix.shape[0], 1)       # the identity: nothing to track
-            return St.overlap_add(est, trk, x.shape[0], H)
+            out = St.overlap_add(est, trk, x.shape[0], H)
+            return out if spk is None else out[:int(self.last_clustering['counts'][0])]
         est = self.infer_chunks(St.chunks(x, L, H), batch_size)
         return St.stitch(est, x.shape[0], H)[0]
 
-    def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out, clustering='chunk', kmeans_init_indices=None, cluster_cap_bytes=None):
+    def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out, clustering='chunk', kmeans_init_indices=None, cluster_cap_bytes=None,
+                            speakers=None, min_score=None):
         from ams_hip import resample as Rs
         Rs.ratio(fs_in, config.fs)                                 # a ValueError before anything is uploaded
         Rs.ratio(config.fs, fs_out)
@@ -847,7 +900,7 @@ class Network(object):
         N = x.shape[0]
         x = Rs.from_pcm16(x, fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs)
         out = self.separate_recording(x, hop=H, batch_size=batch_size, clustering=clustering, kmeans_init_indices=kmeans_init_indices,
-                                      cluster_cap_bytes=cluster_cap_bytes)
+                                      cluster_cap_bytes=cluster_cap_bytes, speakers=speakers, min_score=min_score)
         if fs_out == config.fs:
             return out
         out = Rs.resample(out, config.fs, fs_out)
@@ -855,7 +908,7 @@ class Network(object):
         return out[:, :n_out].contiguous() if n_out < out.shape[1] else out
 
     def separate_recordings(self, xs, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
-                            cluster_cap_bytes=None):
+                            cluster_cap_bytes=None, speakers=None, min_score=None):
         """xs: a list of recordings, float32 [N_r] each (tensors or anything numpy takes) -> a list of [S, N_r] device tensors.  The chunks
         of ALL recordings go through infer_chunks as one stream -- ceil(Ctot / batch_size) model passes instead of one or more per
         recording -- and are cut, tracked and cross-faded by kernels whose launch count does not depend on len(xs)
@@ -873,7 +926,10 @@ class Network(object):
         cross-fade with the identity track table.  kmeans_init_indices: one [tries, clusters] array per recording, over its C_r TF points
         (default: the model's own draw, per recording in list order).  cluster_cap_bytes (default CLUSTER_CAP_BYTES = 8 GiB): the
         embeddings are held for a group of consecutive recordings of at most that many bytes at a time; a recording's result does not
-        depend on the grouping; a single recording above the cap is refused."""
+        depend on the grouping; a single recording above the cap is refused.
+
+        speakers / min_score as in separate_recording: every recording gets its own number of speakers S_r, chosen for all recordings in
+        one counted call whose launches do not depend on len(xs), and its result is [S_r, N_r]."""
         from ams_hip import stitch as St
         from ams_hip import stitch_batch as Sb
         self._refuse_unless_separating()
@@ -883,6 +939,7 @@ class Network(object):
         if not xs:
             raise ValueError('separate_recordings: an empty list of recordings')
         seeds = self._check_clustering(clustering, kmeans_init_indices, len(xs))
+        spk = self._check_speakers(clustering, speakers, min_score)
         L = int(self.args['chunk_size'])
         H = St.default_hop(L) if hop is None else int(hop)
         St.check_geometry(L, H)
@@ -922,10 +979,12 @@ class Network(object):
                 host[o:o + n] = x.detach().cpu().numpy() if torch.is_tensor(x) else x
             mix = Sb.chunks_packed(torch.from_numpy(host).to(device), lay)
         if clustering == 'recording':
-            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes)
+            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes, spk)
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(lay.Ctot, 1)          # the identity: nothing to track
             out = Sb.overlap_add_many(est, trk, lay)
             outs = [out[int(o):int(o) + self.S * int(n)].view(self.S, int(n)) for o, n in zip(lay.out_off, lay.n)]
+            if spk is not None:
+                outs = [o[:int(c)] for o, c in zip(outs, self.last_clustering['counts'].tolist())]       # the first S_r tracks
         else:
             outs = [o for o, _, _ in Sb.stitch_many(self.infer_chunks(mix, batch_size), lay)]
         if not resampled or fs_out == config.fs:
