@@ -248,10 +248,10 @@ def overlap_add_many(est, trk, lay, out=None):
     return out
 
 
-def stitch_many(est, lay):
+def stitch_many(est, lay, packed=False):
     """est [Ctot, S, L] (the model's output for the chunks of chunks_many) -> [(out [S, n_r], trk [C_r, S], Q [C_r - 1, S, S])] per
     recording: views of three packed buffers.  Five launches in all; nothing synchronises with the host once the cross-fade table of
-    this overlap length and the layout's tables are on the device."""
+    this overlap length and the layout's tables are on the device.  packed: return (the packed outputs [out_total], that list)."""
     _est_ok(est, lay, 'stitch_many')
     S = est.shape[1]
     lay.set_sources(S)
@@ -264,4 +264,4 @@ def stitch_many(est, lay):
     for r in range(lay.R):
         o, n = int(lay.out_off[r]), int(lay.n[r])
         res.append((out[o:o + S * n].view(S, n), trks[r], Qs[r][:-1]))
-    return res
+    return (out, res) if packed else res

@@ -1,6 +1,6 @@
 # coding: utf-8
 """python -m experiments.evaluation.separate_many --model_folder ... --sortofmodel {STFT,front}[_enhanced]_{DPCL,L41}
-       (--inputs a.wav b.wav ... | --input_list file) --output_dir D [--hop H] [--resample [--output_rate R]]
+       (--inputs a.wav b.wav ... | --input_list file) --output_dir D [--hop H] [--resample [--output_rate R] [--one_stream]]
 
 Separate many recordings in one call: the chunks of all of them go through the model as one stream of full batches, and they are cut,
 tracked and cross-faded by kernels whose launch count does not depend on the number of recordings (Network.separate_recordings,
@@ -10,7 +10,10 @@ D/<stem>_<k>.wav (.npy for an .npy input), k = 0 .. nb_speakers - 1, where <stem
 two inputs with one stem are refused.
 
 With --resample the inputs are 16-bit PCM .wav files of 1 .. 8 channels at any common rate (they may differ from file to file: the
-files of one rate are separated together); the outputs come back at --output_rate (default: the rate of their input).
+files of one rate are separated together); the outputs come back at --output_rate (default: the rate of their input).  With
+--one_stream the files of ALL rates are separated together, in the order given: one Network.separate_recordings call with the list of
+their rates, one chunk stream, one resampler launch each way.  A chunk's k-means seeds depend on its row in the
+stream, so the results differ from those of the grouping by rate: the flag is opt-in.
 
 With --reference_dir R the separated tracks are scored against the true sources R/<stem>_<k>.wav (.npy for an .npy input), each of
 the input's length: ONE ragged BSS-eval call over all recordings (utils.bss_eval.bss_eval_sources_ragged) with two sets
@@ -47,6 +50,8 @@ def build_parser():
                           'to %d Hz, separate, and resample the outputs back, all on the GPU' % config.fs)
     p.parser.add_argument('--output_rate', type=int, help='Sample rate of the outputs with --resample (default: the rate of each input)',
                           required=False, default=None)
+    p.parser.add_argument('--one_stream', action='store_true', help='With --resample: separate the files of all rates in ONE call and one '
+                          'chunk stream, in the order given, instead of one call per distinct rate (DESIGN.md 4.12)')
     p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
                           "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
                           "(hard k-means only; DESIGN.md 4.10)")
@@ -173,6 +178,8 @@ def main(argv=None):
                          'without them' % args.sortofmodel)
     if args.output_rate is not None and not args.resample:
         raise SystemExit('--output_rate goes with --resample')
+    if args.one_stream and not args.resample:
+        raise SystemExit('--one_stream goes with --resample')
     if args.score_both_clusterings and args.reference_dir is None:
         raise SystemExit('--score_both_clusterings goes with --reference_dir')
     if args.reference_dir is not None and args.resample:
@@ -214,6 +221,11 @@ def main(argv=None):
             xs = [x for x, _ in recs]
             outs = [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=args.clustering)]
             other = (mode, [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=mode)])
+        elif args.resample and args.one_stream:
+            res = model.separate_recordings([x for x, _ in recs], hop=args.hop, fs=[fs for _, fs in recs], output_fs=args.output_rate,
+                                            clustering=args.clustering, **spk)
+            note(range(len(paths)))
+            outs = [o.cpu().numpy() for o in res]
         elif args.resample:
             for fs in sorted(set(fs for _, fs in recs)):          # the files of one rate together
                 idx = [i for i, (_, f) in enumerate(recs) if f == fs]

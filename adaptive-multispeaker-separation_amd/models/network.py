@@ -918,8 +918,13 @@ class Network(object):
         a chunk's row is its place in the stream: separate_recordings(xs)[r] is DEFINED as the stitch of the batched inference.  It is not
         bit-equal to separate_recording(xs[r]) -- except for a single recording, where the rows coincide.
 
-        fs / output_fs as in separate_recording, for float32 [N_r] or int16 frames [N_r, CH] (all of one dtype): every recording goes
-        through the resampler on its own on the way in and out; the separation between is the batched one.
+        fs / output_fs as in separate_recording, for float32 [N_r] or int16 frames [N_r, CH_r] (all of one dtype; CH_r may differ).  fs is
+        one rate for all recordings or a sequence of len(xs) rates; output_fs is None (every recording comes back at its own fs), one rate,
+        or a sequence of len(xs) rates.  All recordings are decoded, mixed down and brought to config.fs in ONE launch, written straight
+        into the packed buffer the chunks are cut from, and go back to their output rates, cut to ceil(N_r output_fs_r / fs_r) samples,
+        in ONE launch (ams_hip.resample_ragged, include/ams_resample_ragged.h): recordings of different rates share one
+        chunk stream.  Every recording's conversion is bit-equal to separate_recording's (ams_hip.resample) on it alone; the results are
+        views of one buffer.  A rate the resampler refuses is a ValueError that names the recording (with a sequence) before any upload.
 
         clustering='recording' (DESIGN.md 4.10): one hard k-means per recording over the embeddings of all its chunks -- all recordings in
         ONE ragged call (ams_hip.kmeans_ragged) between two sweeps of the chunk stream, 2 ceil(Ctot / batch_size) model passes -- and the
@@ -943,8 +948,7 @@ class Network(object):
         L = int(self.args['chunk_size'])
         H = St.default_hop(L) if hop is None else int(hop)
         St.check_geometry(L, H)
-        fs_in = config.fs if fs is None else int(fs)
-        fs_out = fs_in if output_fs is None else int(output_fs)
+        fs_in, fs_out = self._rates(fs, output_fs, len(xs))
         xs = [x if torch.is_tensor(x) else np.asarray(x) for x in xs]
         kinds = set(str(x.dtype).replace('torch.', '') for x in xs)
         if len(kinds) > 1:
@@ -956,20 +960,24 @@ class Network(object):
             if x.ndim not in ((1, 2) if pcm else (1,)) or x.shape[0] < 1:
                 raise ValueError('separate_recordings: float32 [N] or int16 frames [N, CH] of at least one sample, got %s %s'
                                  % (x.dtype, tuple(x.shape)))
-        device = get_default_graph().device
-        resampled = pcm or fs_in != config.fs or fs_out != config.fs
+        resampled = pcm or any(f != config.fs for f in fs_in + fs_out)
         if resampled:
             from ams_hip import resample as Rs
-            Rs.ratio(fs_in, config.fs)                             # a ValueError before anything is uploaded
-            Rs.ratio(config.fs, fs_out)
-            lengths, ys = [x.shape[0] for x in xs], []
-            for x in xs:
-                if not torch.is_tensor(x):
-                    x = torch.from_numpy(np.array(x))              # (a copy: frames read from a file are read-only)
-                x = x.to(device).contiguous()
-                ys.append(Rs.from_pcm16(x.reshape(x.shape[0], -1), fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs))
-            xs = ys
-        if all(torch.is_tensor(x) and x.is_cuda for x in xs):
+            from ams_hip import resample_ragged as Rr
+            named = any(v is not None and not np.isscalar(v) for v in (fs, output_fs))
+            for r in range(len(xs) if named else 1):               # a ValueError before anything is uploaded; a list names the recording
+                try:
+                    Rs.ratio(fs_in[r], config.fs)
+                    Rs.ratio(config.fs, fs_out[r])
+                except ValueError as e:
+                    raise ValueError('recording %d: %s' % (r, e)) if named else e
+            lengths = [x.shape[0] for x in xs]
+        device = get_default_graph().device
+        if resampled:
+            # ONE launch for all recordings' decode, down-mix and rate conversion, straight into the packed buffer of the layout
+            xp, lay = Rr.to_model_rate(xs, fs_in, L=L, H=H, S=self.S, device=device, fs_model=config.fs)
+            mix = Sb.chunks_packed(xp, lay)
+        elif all(torch.is_tensor(x) and x.is_cuda for x in xs):
             mix, lay = Sb.chunks_many([x.contiguous() for x in xs], L, H, self.S)
         else:
             # recordings on the host: packed there and uploaded once
@@ -986,15 +994,30 @@ class Network(object):
             if spk is not None:
                 outs = [o[:int(c)] for o, c in zip(outs, self.last_clustering['counts'].tolist())]       # the first S_r tracks
         else:
-            outs = [o for o, _, _ in Sb.stitch_many(self.infer_chunks(mix, batch_size), lay)]
-        if not resampled or fs_out == config.fs:
+            out, res = Sb.stitch_many(self.infer_chunks(mix, batch_size), lay, packed=True)
+            outs = [o for o, _, _ in res]
+        if not resampled or all(f == config.fs for f in fs_out):
             return outs
-        res = []
-        for out, N in zip(outs, lengths):
-            out = Rs.resample(out.contiguous(), config.fs, fs_out)
-            n_out = -((-N * fs_out) // fs_in)                      # the rule of _separate_resampled
-            res.append(out[:, :n_out].contiguous() if n_out < out.shape[1] else out)
-        return res
+        # ONE launch for all recordings' way back, cut to ceil(N output_fs / fs) samples: N at the rate of the input (the rule of
+        # _separate_resampled; never more than the way back yields)
+        keep = [min(-((-N * fo) // fi), Rs.out_len(int(n), *Rs.ratio(config.fs, fo))) for N, fi, fo, n in zip(lengths, fs_in, fs_out, lay.n)]
+        return Rr.from_model_rate(out, lay, [o.shape[0] for o in outs], fs_out, keep, fs_model=config.fs)
+
+    @staticmethod
+    def _rates(fs, output_fs, R):
+        """(fs_in [R], fs_out [R]) from the fs / output_fs of separate_recordings: None, one rate, or a sequence of R rates."""
+        def many(v, name):
+            if np.isscalar(v):
+                v = [v] * R
+            v = list(v)
+            if len(v) != R:
+                raise ValueError('separate_recordings: %s has %d rates for %d recordings' % (name, len(v), R))
+            for f in v:
+                if not isinstance(f, (int, float, np.integer, np.floating)) or isinstance(f, bool) or int(f) != f:
+                    raise ValueError('separate_recordings: %s: a sample rate is an integer, got %r' % (name, f))
+            return [int(f) for f in v]
+        fs_in = [config.fs] * R if fs is None else many(fs, 'fs')
+        return fs_in, (list(fs_in) if output_fs is None else many(output_fs, 'output_fs'))
 
     def improvement(self, feed_dict, step):
         return self._eval_guarded(feed_dict, lambda run: [self.x_mix.value(run), self.x_non_mix.value(run), self.sdr_imp.value(run)])
