@@ -1,24 +1,25 @@
 // Ragged BSS-eval for gfx950 (include/ams_bss_ragged.h): libams_bss_ragged.so.
 //
-// R recordings of any lengths x K sets of estimates in one call, no FFT.  What does not depend on a recording's length IS the batched
-// code of bss_batch.hip, compiled a second time with AMS_BSS_RAGGED: the blocked f64-MFMA Cholesky and the two triangular solves over
-// all R (1 + S) Gram matrices.  What depends on the length is here, in the time domain, the unit of work (recording, block of
-// AMS_BSSR_BLOCK samples) read from a host-built table:
+// R recordings of any lengths x K sets of estimates in one call, no FFT.  What does not depend on a recording's length is shared with
+// the batched path: the blocked f64-MFMA Cholesky and the two triangular solves over all R (1 + S) Gram matrices (chol_batched.h), the
+// decomposition and the criteria (criteria.h).  What depends on the length is here, in the time domain, the unit of work (recording,
+// block of AMS_BSSR_BLOCK samples) read from a host-built table:
 //   bssr_corr_kernel   u(x, y)[m] = sum_t x[t] y[t + m] over one block, 256 lags per workgroup, as v_mfma_f64_16x16x4_f64 tiles:
 //                      A[i][tau] = x[tau - i], B[tau][j] = y[tau + 16 j]  =>  D[i][j] = u[16 j + i]
 //   bssr_csum_kernel   the block partials of a recording added in block order
-//   bssr_gram_kernel / bssr_rhs_kernel   the layouts of gram_kernel / rhs_kernel of bss_batch.hip
+//   bssr_gram_kernel / bssr_rhs_kernel   the layouts of gram_kernel / rhs_kernel of fft_path.h
 //   bssr_proj_kernel   the FIR projections as the same Toeplitz product, A[i][kappa] = c[i + kappa], B[kappa][j] = x[16 j - kappa]
 //                      =>  D[i][j] = P[16 j + i], and the five sums of sums_kernel in the same launch (no projection reaches memory)
 //   bssr_crit_kernel   the partial rows of a recording added in block order, then the criteria of crit_kernel
 // C/D lane map of the f64 MFMA as in the Cholesky: col = lane & 15, row = (lane >> 4) + 4 reg.  The B operands stride 16 samples from
 // lane to lane; their LDS copies are skewed by one double per 16 (sk) so that the 16 lanes fall on different banks.
 // No atomics, every sum in the order the header states: a result is a function of its recording's data only.
-#define AMS_BSS_RAGGED 1
-static thread_local int g_bssr_enqueued = 0;      // launches of the current ams_bssr_eval call (the reused host code counts through it)
-#define AMS_BSS_LAUNCH(...) do { ++g_bssr_enqueued; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-#include "bss_batch.hip"
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
 #include "../../../include/ams_bss_ragged.h"
+#include "chol_batched.h"
+#include "criteria.h"
 
 namespace {
 
@@ -196,15 +197,7 @@ __global__ __launch_bounds__(256) void bssr_proj_kernel(const double* __restrict
                 if (tt < Lp) {
                     const double s_true = xs[sk(XH + o)];
                     const double ev = tt < L ? er[tt] : 0.0;
-                    const double e_spat = pj[tl][q] - s_true;
-                    const double e_interf = pf[tl][q] - s_true - e_spat;
-                    const double e_artif = -s_true - e_spat - e_interf + ev;
-                    const double s_filt = s_true + e_spat;
-                    s0 += s_filt * s_filt;
-                    s1 += (e_interf + e_artif) * (e_interf + e_artif);
-                    s2 += e_interf * e_interf;
-                    s3 += (s_filt + e_interf) * (s_filt + e_interf);
-                    s4 += e_artif * e_artif;
+                    decompose_add(s_true, pj[tl][q], pf[tl][q], ev, s0, s1, s2, s3, s4);
                 }
             }
         double* out = part + (((long)row * KS + e) * S + j) * 5;
@@ -227,18 +220,12 @@ __global__ void bssr_crit_kernel(const double* __restrict__ part, const long* __
     double s[5] = {0, 0, 0, 0, 0};
     for (long b = b_off[r]; b < b_off[r + 1]; ++b)
         for (int k = 0; k < 5; ++k) s[k] += part[((b * KS * S) + pair) * 5 + k];
-    const double nanv = nan("");
     const int set = pair / (S * S), ej = pair % (S * S), K = KS / S;
-    double* out = crit + ((long)r * K + set) * 3 * S * S;
-    out[0 * S * S + ej] = bad ? nanv : 10.0 * log10(s[0] / (s[1] + 1e-12));
-    out[1 * S * S + ej] = bad ? nanv : 10.0 * log10(s[0] / (s[2] + 1e-12));
-    out[2 * S * S + ej] = bad ? nanv : 10.0 * log10(s[3] / (s[4] + 1e-12));
+    criteria_store(s, bad, crit + ((long)r * K + set) * 3 * S * S, S * S, ej);
     if (pair == 0) info_out[r] = bad;
 }
 
 bool bssr_domain(int S, int K, int F) { return S >= 1 && S <= 6 && K >= 1 && K <= 64 && F >= 1 && F <= MAXF; }
-
-int potrf_launches(int n) { return 3 * ((n + NB - 1) / NB) - 2; }     // potrf_batched: diag, and panel + trail for all but the last
 
 struct bssr_layout {
     size_t G, Gj, Df, Dj, corr, cpart, part, info, total;
@@ -326,22 +313,25 @@ int ams_bssr_eval(const double* ref, const double* est, const int64_t* l_off, co
     const long* lo = (const long*)l_off;
     const long* bo = (const long*)b_off;
 
-    g_bssr_enqueued = 0;
-    AMS_BSS_LAUNCH(bssr_corr_kernel, dim3((unsigned)Btot, NU, (F + 255) / 256), dim3(256), 0, st, ref, est, lo, tab, cpart, S, KS, F);
-    AMS_BSS_LAUNCH(bssr_csum_kernel, dim3((NU * F + 255) / 256, R), dim3(256), 0, st, cpart, bo, corr, NU * F);
+    hipLaunchKernelGGL(bssr_corr_kernel, dim3((unsigned)Btot, NU, (F + 255) / 256), dim3(256), 0, st, ref, est, lo, tab, cpart, S, KS, F);
+    hipLaunchKernelGGL(bssr_csum_kernel, dim3((NU * F + 255) / 256, R), dim3(256), 0, st, cpart, bo, corr, NU * F);
     const long nn = (long)N * N;
-    AMS_BSS_LAUNCH(bssr_gram_kernel, dim3((unsigned)(nn + 255 < 1024 * 256 ? (nn + 255) / 256 : 1024), R), dim3(256), 0, st, corr, G, Gj, S,
-                   KS, F);
-    AMS_BSS_LAUNCH(bssr_rhs_kernel, dim3((KS * N + 255) / 256 < 16 ? (KS * N + 255) / 256 : 16, R), dim3(256), 0, st, corr, Df, Dj, S, KS, F);
+    hipLaunchKernelGGL(bssr_gram_kernel, dim3((unsigned)(nn + 255 < 1024 * 256 ? (nn + 255) / 256 : 1024), R), dim3(256), 0, st, corr, G,
+                       Gj, S, KS, F);
+    hipLaunchKernelGGL(bssr_rhs_kernel, dim3((KS * N + 255) / 256 < 16 ? (KS * N + 255) / 256 : 16, R), dim3(256), 0, st, corr, Df, Dj, S,
+                       KS, F);
     // factorise every Gram matrix once, then solve with all estimates of all sets as right-hand sides (as ams_bssb_eval)
-    if (potrf_batched(G, N, N, nn, R, info_f, st) != 0) return -3;
-    if (potrf_batched(Gj, F, F, (long)F * F, R * S, info_j, st) != 0) return -3;
-    solve_batched(G, N, N, nn, Df, N, (long)KS * N, KS, R, st);
-    solve_batched(Gj, F, F, (long)F * F, Dj, F, (long)KS * F, KS, R * S, st);
-    AMS_BSS_LAUNCH(bssr_proj_kernel, dim3((unsigned)Btot, KS), dim3(256), 0, st, ref, est, lo, tab, Df, Dj, part, S, KS, F);
-    AMS_BSS_LAUNCH(bssr_crit_kernel, dim3(KS * S, R), dim3(64), 0, st, part, bo, info_f, info_j, crit, info, S, KS);
+    const int pf = potrf_batched(G, N, N, nn, R, info_f, st);
+    if (pf < 0) return -3;
+    const int pj = potrf_batched(Gj, F, F, (long)F * F, R * S, info_j, st);
+    if (pj < 0) return -3;
+    const int sf = solve_batched(G, N, N, nn, Df, N, (long)KS * N, KS, R, st);
+    const int sj = solve_batched(Gj, F, F, (long)F * F, Dj, F, (long)KS * F, KS, R * S, st);
+    hipLaunchKernelGGL(bssr_proj_kernel, dim3((unsigned)Btot, KS), dim3(256), 0, st, ref, est, lo, tab, Df, Dj, part, S, KS, F);
+    hipLaunchKernelGGL(bssr_crit_kernel, dim3(KS * S, R), dim3(64), 0, st, part, bo, info_f, info_j, crit, info, S, KS);
     if (hipGetLastError() != hipSuccess) return -3;
-    return g_bssr_enqueued == ams_bssr_launches(S, K, F) ? 0 : -3;
+    // the header's promise: this call's six launches and what the shared code reports are what ams_bssr_launches states
+    return 4 + pf + pj + sf + sj + 2 == ams_bssr_launches(S, K, F) ? 0 : -3;
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@ class BssError(RuntimeError):
 
 
 def _load():
+    """libams_bss.so with both of its interfaces declared: ams_bss_* (include/ams_bss.h) and ams_bssb_* (include/ams_bss_batch.h)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -40,10 +41,29 @@ def _load():
         lib.ams_bss_workspace_bytes.argtypes = [ctypes.c_void_p]
         lib.ams_bss_eval_pairs.restype = ctypes.c_int
         lib.ams_bss_eval_pairs.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.ams_bssb_abi_version.restype = ctypes.c_int
+        lib.ams_bssb_create.restype = ctypes.c_int
+        lib.ams_bssb_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 5
+        lib.ams_bssb_destroy.restype = None
+        lib.ams_bssb_destroy.argtypes = [ctypes.c_void_p]
+        lib.ams_bssb_workspace_bytes.restype = ctypes.c_size_t
+        lib.ams_bssb_workspace_bytes.argtypes = [ctypes.c_void_p]
+        lib.ams_bssb_eval.restype = ctypes.c_int
+        lib.ams_bssb_eval.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
+        lib.ams_bssb_potrf.restype = ctypes.c_int
+        lib.ams_bssb_potrf.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_void_p]
         if lib.ams_bss_abi_version() != 1:
             raise BssError('libams_bss.so ABI version mismatch')
+        if lib.ams_bssb_abi_version() != 1:
+            raise BssError('libams_bss.so batch ABI version mismatch')
         _lib = lib
     return _lib
+
+
+def _load_batch():
+    """The same library, under the name the batched path, tools/bss_bench.py and the tests use."""
+    return _load()
 
 
 def _context(nsrc, nsampl, flen, device):
@@ -91,16 +111,7 @@ def bss_eval_sources_cupy(reference_sources, estimated_sources, compute_permutat
                                    else reference_sources.reshape(nsrc, -1),
                                    np.asarray(estimated_sources).reshape(nsrc, -1) if not torch.is_tensor(estimated_sources)
                                    else estimated_sources.reshape(nsrc, -1))
-    dum = np.arange(nsrc)
-    if not compute_permutation:
-        return sdr[dum, dum], sir[dum, dum], sar[dum, dum], dum
-    perms = list(itertools.permutations(list(range(nsrc))))
-    mean_sir = np.empty(len(perms))
-    for i, perm in enumerate(perms):
-        mean_sir[i] = np.mean(sir[list(perm), dum])
-    popt = perms[int(np.argmax(mean_sir))]
-    idx = (list(popt), dum)
-    return sdr[idx], sir[idx], sar[idx], np.asarray(popt)
+    return _select_permutation(sdr, sir, sar, compute_permutation)
 
 
 # the reference exposes the same metric under two names (numpy and cupy back ends); both map to the HIP path here
@@ -112,32 +123,7 @@ bss_eval_sources = bss_eval_sources_cupy
 # utterance are assembled and factorised once (the library's own batched MFMA-f64 Cholesky) and shared by its K sets.
 MAX_UTT = 64                    # utterances per library call; larger batches are processed in slices of this size
 
-_blib = None
 _bctx = {}                      # (max_utt, nsets, nsrc, nsampl, flen, device) -> (ctx pointer, workspace tensor, bytes)
-
-
-def _load_batch():
-    global _blib
-    if _blib is None:
-        if not os.path.exists(LIB_PATH):
-            raise BssError('libams_bss.so not found at %s -- run __graft_entry__.build() (no CPU fallback)' % LIB_PATH)
-        lib = ctypes.CDLL(LIB_PATH)
-        lib.ams_bssb_abi_version.restype = ctypes.c_int
-        lib.ams_bssb_create.restype = ctypes.c_int
-        lib.ams_bssb_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 5
-        lib.ams_bssb_destroy.restype = None
-        lib.ams_bssb_destroy.argtypes = [ctypes.c_void_p]
-        lib.ams_bssb_workspace_bytes.restype = ctypes.c_size_t
-        lib.ams_bssb_workspace_bytes.argtypes = [ctypes.c_void_p]
-        lib.ams_bssb_eval.restype = ctypes.c_int
-        lib.ams_bssb_eval.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
-        lib.ams_bssb_potrf.restype = ctypes.c_int
-        lib.ams_bssb_potrf.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
-                                       ctypes.c_void_p]
-        if lib.ams_bssb_abi_version() != 1:
-            raise BssError('libams_bss.so batch ABI version mismatch')
-        _blib = lib
-    return _blib
 
 
 def _batch_context(max_utt, nsets, nsrc, nsampl, flen, device):
@@ -194,8 +180,8 @@ def bss_eval_pairs_batch(reference_sources, estimated_sources, flen=FLEN, max_ut
 
 
 def _select_permutation(sdr, sir, sar, compute_permutation=True):
-    """[S, S] pair matrices -> (sdr, sir, sar [S], perm [S]); the rule of bss_eval_sources_cupy: best mean SIR, the first
-    maximum wins."""
+    """[S, S] pair matrices -> (sdr, sir, sar [S], perm [S]); the rule of the reference's bss_eval_sources_cupy (:613-620): best
+    mean SIR, the first maximum wins."""
     nsrc = sir.shape[0]
     dum = np.arange(nsrc)
     if not compute_permutation:
@@ -209,10 +195,8 @@ def _select_permutation(sdr, sir, sar, compute_permutation=True):
     return sdr[idx], sir[idx], sar[idx], np.asarray(popt)
 
 
-def bss_eval_sources_batch(reference_sources, estimated_sources, compute_permutation=True, flen=FLEN, max_utt=MAX_UTT):
-    """refs [U, S, L], ests [U, S, L] or [U, K, S, L] -> (sdr, sir, sar [U, K, S] float64, perm [U, K, S] int): per utterance and
-    set what bss_eval_sources_cupy returns, from ONE library call per slice of max_utt utterances."""
-    crit, _ = bss_eval_pairs_batch(reference_sources, estimated_sources, flen=flen, max_utt=max_utt)
+def _select_all(crit, compute_permutation):
+    """crit [U, K, 3, S, S] -> (sdr, sir, sar [U, K, S] float64, perm [U, K, S] int): _select_permutation per (unit, set)."""
     U, K, _, S, _ = crit.shape
     sdr, sir, sar = (np.empty((U, K, S)) for _ in range(3))
     perm = np.empty((U, K, S), dtype=np.int64)
@@ -221,6 +205,13 @@ def bss_eval_sources_batch(reference_sources, estimated_sources, compute_permuta
             sdr[u, k], sir[u, k], sar[u, k], perm[u, k] = _select_permutation(crit[u, k, 0], crit[u, k, 1], crit[u, k, 2],
                                                                               compute_permutation)
     return sdr, sir, sar, perm
+
+
+def bss_eval_sources_batch(reference_sources, estimated_sources, compute_permutation=True, flen=FLEN, max_utt=MAX_UTT):
+    """refs [U, S, L], ests [U, S, L] or [U, K, S, L] -> (sdr, sir, sar [U, K, S] float64, perm [U, K, S] int): per utterance and
+    set what bss_eval_sources_cupy returns, from ONE library call per slice of max_utt utterances."""
+    crit, _ = bss_eval_pairs_batch(reference_sources, estimated_sources, flen=flen, max_utt=max_utt)
+    return _select_all(crit, compute_permutation)
 
 
 def potrf_batch(a):
@@ -445,11 +436,4 @@ def bss_eval_sources_ragged(refs, ests, compute_permutation=True, flen=FLEN, cap
     """As bss_eval_pairs_ragged -> (sdr, sir, sar [R, K, S] float64, perm [R, K, S] int): per recording and set what
     bss_eval_sources_cupy returns."""
     crit, _ = bss_eval_pairs_ragged(refs, ests, flen=flen, cap_bytes=cap_bytes)
-    R, K, _, S, _ = crit.shape
-    sdr, sir, sar = (np.empty((R, K, S)) for _ in range(3))
-    perm = np.empty((R, K, S), dtype=np.int64)
-    for r in range(R):
-        for k in range(K):
-            sdr[r, k], sir[r, k], sar[r, k], perm[r, k] = _select_permutation(crit[r, k, 0], crit[r, k, 1], crit[r, k, 2],
-                                                                              compute_permutation)
-    return sdr, sir, sar, perm
+    return _select_all(crit, compute_permutation)

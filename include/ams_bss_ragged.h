@@ -4,8 +4,8 @@
  * points score R recordings of ANY lengths, each against K sets of estimates, in one call: the number of kernel launches is a function
  * of (S, K, F) only, there is no context, no FFT plan and no hipFFT / hipSOLVER on the link line.  The correlations and the projections
  * are computed in the time domain with v_mfma_f64_16x16x4_f64; the Gram matrices are factorised and solved by the batched blocked
- * Cholesky and triangular solves of csrc/bss/bss_batch.hip, compiled a second time into this library.  ams_bss.h and ams_bss_batch.h
- * are unchanged and keep their own version numbers.
+ * Cholesky and triangular solves of csrc/bss/chol_batched.h, the header the batched path (ams_bss_batch.h) builds from too.  ams_bss.h
+ * and ams_bss_batch.h are unchanged and keep their own version numbers.
  *
  * Conventions: 0 on success, <0 on error (-1 invalid argument, returned before anything is launched; -2 workspace too small, nothing
  * launched; -3 launch failure), as ams_bss_batch.h.  The entry points never allocate and never synchronise; they enqueue on the given
@@ -33,12 +33,13 @@
  *                 u(ref_i, ref_j)[-m] for m < 0;  re_ie[k] = u(ref_i, est_e)[k].  Every lag of every pair is computed once and both
  *                 Gram blocks (i, j) and (j, i) are filled from it.
  *   Gram          G [S F, S F] column-major, block (i, j) element [a, b] = rr_ij[b - a];  Gj[i] = the diagonal block (i, i) [F, F];
- *                 Df[e][i F + k] = Dj[i][e][k] = re_ie[k]  -- the layouts of gram_kernel / rhs_kernel of bss_batch.hip.
+ *                 Df[e][i F + k] = Dj[i][e][k] = re_ie[k]  -- the layouts of gram_kernel / rhs_kernel of csrc/bss/fft_path.h.
  *   Solves        Cf[e] = G^-1 Df[e] (filters of estimate e on all references), Cj[j][e] = Gj[j]^-1 Dj[j][e], in place.
  *   Projections   P_f(e)[t] = sum_i sum_k Cf_{e,i}[k] ref_i[t - k],  P_j(e)[t] = sum_k Cj_{j,e}[k] ref_j[t - k],  t = 0 .. L_r + F - 2,
  *                 never written to memory: the five sums of sums_kernel are taken where the projections are formed, through
- *                 s_true = ref_j, e_spat = P_j - s_true, e_interf = P_f - s_true - e_spat, e_artif = -s_true - e_spat - e_interf + est.
- *   Criteria      10 log10(num / (den + 1e-12)), as crit_kernel.
+ *                 s_true = ref_j, e_spat = P_j - s_true, e_interf = P_f - s_true - e_spat, e_artif = -s_true - e_spat - e_interf + est
+ *                 (csrc/bss/criteria.h, one function for all paths).
+ *   Criteria      10 log10(num / (den + 1e-12)), as crit_kernel (csrc/bss/criteria.h).
  * Summation order (fixed; no atomics on floating-point data; a result is a function of its recording's data only).
  *   Correlations: per (block, pair, tile of 256 lags) one workgroup of four waves.  The block is two halves of 2048 samples; a half is
  *   2048 / 4 + 4 MFMA steps of four consecutive tau (tau = t + lag mod 16); wave w takes the steps 129 w .. 129 w + 128 of each

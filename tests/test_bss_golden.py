@@ -6,31 +6,14 @@ dB tolerance: 1e-6 dB where the criterion is below 100 dB; criteria above 100 dB
 rounding floor (e.g. SAR of "mixture as estimate": the estimate lies exactly in the span of the references) and are only
 required to stay above 100 dB on both sides.
 """
-import os
 
 import numpy as np
 import pytest
 
 from oracle import bss_eval as obss
+from tests.bss_common import G, close_db as _close_db, cupy_db as _cupy_db
 
-G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'bss_eval.npz'))
 CASES = sorted({k.split('/')[0] for k in G.files if k.startswith('n')})
-TOL_DB = 1e-6
-
-
-def _close_db(got, ref, tol=TOL_DB):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    small = ref < 100.0
-    assert np.abs(got[small] - ref[small]).max(initial=0.0) < tol, (got, ref)
-    assert (got[~small] > 100.0).all(), (got, ref)
-
-
-def _cupy_db(name):
-    """The reference's GPU-path dB convention (_safe_db_cupy, utils/bss_eval.py:742-748) from the stored reference energies."""
-    e = G[name + '/energies']
-    ea = G[name + '/e_artif_energy']
-    db = lambda num, den: 10.0 * np.log10(num / (den + 1e-12))      # noqa: E731
-    return np.stack([db(e[..., 0], e[..., 1]), db(e[..., 0], e[..., 2]), db(e[..., 3], ea)])
 
 
 @pytest.mark.parametrize('name', CASES)

@@ -14,6 +14,7 @@ import pytest
 
 from oracle import bss_eval as obss
 from tests import bss_ragged_ref as rr
+from tests.bss_common import close_db as _close_db, mix as _mix
 
 torch = pytest.importorskip('torch')
 
@@ -21,10 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, 'adaptive-multispeaker-separation_amd', 'ams_hip')
 NAMES = {'ams_bssr_abi_version', 'ams_bssr_block', 'ams_bssr_blocks', 'ams_bssr_tables', 'ams_bssr_launches', 'ams_bssr_workspace_bytes',
          'ams_bssr_eval'}
-# what libams_bss.so exports (include/ams_bss.h and include/ams_bss_batch.h); the ragged build of bss_batch.hip must not change it
+# what libams_bss.so exports (include/ams_bss.h and include/ams_bss_batch.h); sharing csrc/bss/chol_batched.h with the ragged library must not change it
 BSS_NAMES = {'ams_bss_abi_version', 'ams_bss_create', 'ams_bss_destroy', 'ams_bss_workspace_bytes', 'ams_bss_eval_pairs',
              'ams_bssb_abi_version', 'ams_bssb_create', 'ams_bssb_destroy', 'ams_bssb_workspace_bytes', 'ams_bssb_eval', 'ams_bssb_potrf'}
-TOL_DB = 1e-6
 vp = ctypes.c_void_p
 
 
@@ -37,16 +37,6 @@ def _built():
 def _exports(path):
     out = subprocess.run(['nm', '-D', '--defined-only', path], capture_output=True, text=True, check=True).stdout
     return {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith('ams_')}
-
-
-def _close_db(got, ref, tol=TOL_DB):                          # tests/test_bss_golden.py's rule
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    small = ref < 100.0
-    err = np.abs(got[small] - ref[small]).max(initial=0.0)
-    print('max |dB error| below 100 dB: %.3e (tol %.1e); min above: %s' % (err, tol, got[~small].min(initial=np.inf)))
-    assert err < tol, (got, ref)
-    assert (got[~small] > 100.0).all(), (got, ref)
-    return err
 
 
 def test_header_and_exports():
@@ -232,15 +222,6 @@ def test_sources_ragged_permutation_rule(monkeypatch):
             want = hb._select_permutation(crit[r, k, 0], crit[r, k, 1], crit[r, k, 2])
             assert np.array_equal(perm[r, k], want[3]) and np.array_equal(sdr[r, k], crit[r, k, 0][perm[r, k], dum])
     assert np.array_equal(hb.bss_eval_sources_ragged(None, None, compute_permutation=False)[3], np.broadcast_to(dum, (R, K, S)))
-
-
-def _mix(rng, nsrc, L):                                       # as tests/test_gpu_bss_batch.py
-    s = rng.randn(nsrc, L)
-    for i in range(nsrc):
-        s[i] = np.convolve(s[i], rng.randn(8 + 3 * i), mode='same')
-    a = rng.randn(nsrc, nsrc) * 0.3 + np.eye(nsrc)
-    est = a.dot(s) + 0.05 * rng.randn(nsrc, L)
-    return s, est
 
 
 @pytest.mark.parametrize('S,K,L', [(2, 1, 100), (2, 1, 257), (2, 1, 4097), (3, 2, 1000)])

@@ -3,8 +3,6 @@ oracle and the per-utterance path, plus the properties the batch must keep: a re
 silent reference poisons its own utterance only, slicing changes nothing, and the f64 MFMA lane map is the right one.
 
 dB rule (tests/test_bss_golden.py, unchanged): 1e-6 dB where the expected value is below 100 dB, "stays above 100 dB" above."""
-import os
-
 import numpy as np
 import pytest
 
@@ -12,34 +10,7 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 from oracle import bss_eval as obss
-
-G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'bss_eval.npz'))
-TOL_DB = 1e-6
-
-
-def _close_db(got, ref, tol=TOL_DB):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    small = ref < 100.0
-    err = np.abs(got[small] - ref[small]).max(initial=0.0)
-    print('max |dB error| below 100 dB: %.3e (tol %.1e); min above: %s' % (err, tol, got[~small].min(initial=np.inf)))
-    assert err < tol, (got, ref)
-    assert (got[~small] > 100.0).all(), (got, ref)
-
-
-def _cupy_db(name):
-    e = G[name + '/energies']
-    ea = G[name + '/e_artif_energy']
-    db = lambda num, den: 10.0 * np.log10(num / (den + 1e-12))      # noqa: E731
-    return np.stack([db(e[..., 0], e[..., 1]), db(e[..., 0], e[..., 2]), db(e[..., 3], ea)])
-
-
-def _mix(rng, nsrc, L):                                       # as tests/test_gpu_bss_eval.py
-    s = rng.randn(nsrc, L)
-    for i in range(nsrc):
-        s[i] = np.convolve(s[i], rng.randn(8 + 3 * i), mode='same')
-    a = rng.randn(nsrc, nsrc) * 0.3 + np.eye(nsrc)
-    est = a.dot(s) + 0.05 * rng.randn(nsrc, L)
-    return s, est
+from tests.bss_common import G, close_db as _close_db, cupy_db as _cupy_db, mix as _mix, oracle as _oracle
 
 
 def _batch(seed, U, K, nsrc, L):
@@ -51,16 +22,6 @@ def _batch(seed, U, K, nsrc, L):
         for k in range(1, K):
             ests[u, k] = e + 0.2 * k * rng.randn(nsrc, L)
     return refs, ests
-
-
-def _oracle(refs, ests, flen):
-    U, K, S, _ = ests.shape
-    crit, perm = np.empty((U, K, 3, S, S)), np.empty((U, K, S), np.int64)
-    for u in range(U):
-        for k in range(K):
-            r = obss.bss_eval_sources(refs[u], ests[u, k], flen=flen, return_matrices=True)
-            crit[u, k], perm[u, k] = np.stack(r[4]), r[3]
-    return crit, perm
 
 
 @pytest.mark.parametrize('names', [('n2_L20480', 'n2_mixture_as_estimate'), ('n2_L3000', 'n2_near_silent_estimate'),

@@ -7,15 +7,7 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 from oracle import bss_eval as obss
-
-
-def _mix(rng, nsrc, L):
-    s = rng.randn(nsrc, L)
-    for i in range(nsrc):                                     # colour the sources so the Gram matrices are not near-identity
-        s[i] = np.convolve(s[i], rng.randn(8 + 3 * i), mode='same')
-    a = rng.randn(nsrc, nsrc) * 0.3 + np.eye(nsrc)
-    est = a.dot(s) + 0.05 * rng.randn(nsrc, L)
-    return s, est
+from tests.bss_common import mix as _mix
 
 
 @pytest.mark.parametrize('nsrc,L', [(2, 3000), (3, 2500), (2, 20480)])

@@ -5,7 +5,6 @@ nothing outside the operands is touched, and a short workspace launches nothing.
 
 dB rule (tests/test_bss_golden.py, unchanged): 1e-6 dB where the expected value is below 100 dB, "stays above 100 dB" above."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -14,34 +13,7 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 from oracle import bss_eval as obss
-
-G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'bss_eval.npz'))
-TOL_DB = 1e-6
-
-
-def _close_db(got, ref, tol=TOL_DB):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    small = ref < 100.0
-    err = np.abs(got[small] - ref[small]).max(initial=0.0)
-    print('max |dB error| below 100 dB: %.3e (tol %.1e); min above: %s' % (err, tol, got[~small].min(initial=np.inf)))
-    assert err < tol, (got, ref)
-    assert (got[~small] > 100.0).all(), (got, ref)
-
-
-def _cupy_db(name):                                           # as tests/test_gpu_bss_batch.py
-    e = G[name + '/energies']
-    ea = G[name + '/e_artif_energy']
-    db = lambda num, den: 10.0 * np.log10(num / (den + 1e-12))      # noqa: E731
-    return np.stack([db(e[..., 0], e[..., 1]), db(e[..., 0], e[..., 2]), db(e[..., 3], ea)])
-
-
-def _mix(rng, nsrc, L):                                       # as tests/test_gpu_bss_batch.py
-    s = rng.randn(nsrc, L)
-    for i in range(nsrc):
-        s[i] = np.convolve(s[i], rng.randn(8 + 3 * i), mode='same')
-    a = rng.randn(nsrc, nsrc) * 0.3 + np.eye(nsrc)
-    est = a.dot(s) + 0.05 * rng.randn(nsrc, L)
-    return s, est
+from tests.bss_common import G, close_db as _close_db, cupy_db as _cupy_db, mix as _mix, oracle as _oracle
 
 
 def _ragged(seed, lengths, K, nsrc):
@@ -53,17 +25,6 @@ def _ragged(seed, lengths, K, nsrc):
         refs.append(r)
         ests.append(np.stack([e[::-1]] + [e + 0.2 * k * rng.randn(nsrc, L) for k in range(1, K)]))
     return refs, ests
-
-
-def _oracle(refs, ests, flen):
-    """crit [R, K, 3, S, S] and perm [R, K, S] from oracle/bss_eval.py on each recording alone."""
-    R, (K, S, _) = len(refs), ests[0].shape
-    crit, perm = np.empty((R, K, 3, S, S)), np.empty((R, K, S), np.int64)
-    for r in range(R):
-        for k in range(K):
-            o = obss.bss_eval_sources(refs[r], ests[r][k], flen=flen, return_matrices=True)
-            crit[r, k], perm[r, k] = np.stack(o[4]), o[3]
-    return crit, perm
 
 
 def _lengths():

@@ -13,20 +13,11 @@ torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
 from oracle import bss_eval as obss
+from tests.bss_common import TOL_DB, close_db as _close_db
 from tests.test_gpu_separate_recording import B, L, S, STEPS, TRIES, _front, _recording
 from tests.test_gpu_separate_recordings import LENGTHS
 
-TOL_DB = 1e-6
 _RUNS = {}
-
-
-def _close_db(got, ref, tol=TOL_DB):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    small = ref < 100.0
-    err = np.abs(got[small] - ref[small]).max(initial=0.0)
-    print('max |dB error| below 100 dB: %.3e (tol %.1e); min above: %s' % (err, tol, got[~small].min(initial=np.inf)))
-    assert err < tol, (got, ref)
-    assert (got[~small] > 100.0).all(), (got, ref)
 
 
 def _runs():

@@ -1,7 +1,7 @@
 """Ragged BSS-eval: one call over recordings of different lengths against the loop of batched calls: one JSON line.
 
 R = 256 recordings, S = 2 sources, K = 2 sets of estimates, flen = 512: lengths of 4 .. 12 s at 8 kHz drawn (RandomState(7)) from 16
-distinct values, the signals by the _mix / _batch construction of tests/test_gpu_bss_batch.py (RandomState(9)), float64 on the device.
+distinct values, the signals by the mix construction of tests/bss_common.py (RandomState(9)), float64 on the device.
     (a) loop_ms     for r: utils.bss_eval.bss_eval_pairs_batch(ref_r[None], est_r[None])     the existing code: one cached context
                     (four hipFFT plans and a workspace) per distinct length -- 16 here, created during warm-up
     (b) ragged_ms   utils.bss_eval.bss_eval_pairs_ragged(refs, ests)                         ONE library call, no plan
@@ -33,7 +33,7 @@ F64_MATRIX_TFLOPS = 78.6
 TOL_DB = 1e-6
 
 
-def _mix(rng, nsrc, L):                                       # as tests/test_gpu_bss_batch.py
+def _mix(rng, nsrc, L):                                       # as tests/bss_common.py
     s = rng.randn(nsrc, L)
     for i in range(nsrc):
         s[i] = np.convolve(s[i], rng.randn(8 + 3 * i), mode='same')
