@@ -11,6 +11,9 @@ With --clustering recording, --speakers auto (2 .. nb_speakers) or --speakers LO
  and k = 0 .. S_r - 1 are written; LO = 1 needs --min_score X, the score below which the recording counts as one
 speaker.
 
+--clustering recording_soft is the recording-level mode of a model with a soft k-means (--beta_kmeans): one soft
+k-means over the embeddings of all chunks, its soft labels as the masks.
+
 With --resample the input may be a 16-bit PCM .wav of 1 .. 8 channels at any rate whose reduced ratio to config.fs has both terms in
 1 .. 1024 (every standard rate from 11025 to 96000 Hz), or an .npy float32 [N] at --input_rate.  The frames are uploaded as they are;
 decoding, the channel down-mix and the way to config.fs are one GPU kernel, the separated tracks go back to --output_rate (default: the
@@ -39,9 +42,10 @@ def build_parser():
                           required=False, default=None)
     p.parser.add_argument('--input_rate', type=int, help='Sample rate of an .npy input (required with --resample and .npy)',
                           required=False, default=None)
-    p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
-                          "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
-                          "(hard k-means only; DESIGN.md 4.10)")
+    p.parser.add_argument('--clustering', choices=['chunk', 'recording', 'recording_soft'], default='chunk', help="k-means per chunk with "
+                          "the outputs tracked across the chunk borders (default), or ONE k-means per recording over the embeddings of all "
+                          "its chunks: 'recording' for a hard k-means (DESIGN.md 4.10), 'recording_soft' for a model with --beta_kmeans "
+                          "(DESIGN.md 4.13)")
     add_speakers_args(p.parser)
     p.add_adapt_args()
     p.add_separator_args()

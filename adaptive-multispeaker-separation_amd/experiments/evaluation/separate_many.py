@@ -20,7 +20,8 @@ the input's length: ONE ragged BSS-eval call over all recordings (utils.bss_eval
 of estimates per recording -- the mixture repeated nb_speakers times (the "no separation" line of eval.py) and the tracks as they were
 written -- and D/scores.json holds the criteria per recording, their means and the mean improvement over the mixture.
 --score_both_clusterings separates under both clusterings, writes the tracks of the one --clustering names and scores both as a third
-set of the same call.  Scoring is at the model's rate only: --reference_dir with --resample is refused.
+set of the same call (with --clustering recording_soft, for a model with --beta_kmeans, the pair is 'chunk' and 'recording_soft':
+DESIGN.md 4.13).  Scoring is at the model's rate only: --reference_dir with --resample is refused.
 
 With --clustering recording, --speakers auto|LO:HI (and --min_score X for LO = 1) chooses every recording's number of speakers S_r
 (DESIGN.md 4.11): D/<stem>_0 .. D/<stem>_{S_r - 1} are written, and D/counts.json holds every stem's count and the scores of its
@@ -52,13 +53,15 @@ def build_parser():
                           required=False, default=None)
     p.parser.add_argument('--one_stream', action='store_true', help='With --resample: separate the files of all rates in ONE call and one '
                           'chunk stream, in the order given, instead of one call per distinct rate (DESIGN.md 4.12)')
-    p.parser.add_argument('--clustering', choices=['chunk', 'recording'], default='chunk', help="k-means per chunk with the outputs tracked "
-                          "across the chunk borders (default), or ONE k-means per recording over the embeddings of all its chunks "
-                          "(hard k-means only; DESIGN.md 4.10)")
+    p.parser.add_argument('--clustering', choices=['chunk', 'recording', 'recording_soft'], default='chunk', help="k-means per chunk with "
+                          "the outputs tracked across the chunk borders (default), or ONE k-means per recording over the embeddings of all "
+                          "its chunks: 'recording' for a hard k-means (DESIGN.md 4.10), 'recording_soft' for a model with --beta_kmeans "
+                          "(DESIGN.md 4.13)")
     p.parser.add_argument('--reference_dir', help='Score the separated tracks against the true sources <reference_dir>/<stem>_<k>.wav '
                           '(.npy for an .npy input) and write <output_dir>/scores.json (DESIGN.md 6c)', required=False, default=None)
     p.parser.add_argument('--score_both_clusterings', action='store_true', help="With --reference_dir: separate under 'chunk' and "
-                          "under 'recording', write the tracks of the one --clustering names, score both in the same call")
+                          "under 'recording' ('recording_soft' where --clustering names it), write the tracks of the one --clustering "
+                          "names, score both in the same call")
     one.add_speakers_args(p.parser)
     p.add_adapt_args()
     p.add_separator_args()
@@ -216,8 +219,10 @@ def main(argv=None):
         if args.score_both_clusterings:
             # a soft k-means model is refused here, with the message clustering='recording' gives, before anything is separated; the
             # clustering whose tracks are written runs first, so that it draws the k-means seeds it draws without scoring
-            model._check_clustering('recording', None, len(recs))
-            mode = 'recording' if args.clustering == 'chunk' else 'chunk'
+            # (--clustering recording_soft: the pair is 'chunk' and 'recording_soft', and a hard model is refused the same way)
+            whole = 'recording_soft' if args.clustering == 'recording_soft' else 'recording'
+            model._check_clustering(whole, None, len(recs))
+            mode = whole if args.clustering == 'chunk' else 'chunk'
             xs = [x for x, _ in recs]
             outs = [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=args.clustering)]
             other = (mode, [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=mode)])
@@ -259,7 +264,7 @@ def main(argv=None):
         sets = [(args.clustering if other else 'separated', [as_written(o, n) for o, n in zip(outs, npy)])]
         if other:
             sets.append((other[0], [as_written(o, n) for o, n in zip(other[1], npy)]))
-            sets.sort(key=lambda s: ('chunk', 'recording').index(s[0]))
+            sets.sort(key=lambda s: ('chunk', 'recording', 'recording_soft').index(s[0]))
         scores = score(paths, recs, refs, sets)
         sp = os.path.join(args.output_dir, 'scores.json')
         with open(sp, 'w') as f:

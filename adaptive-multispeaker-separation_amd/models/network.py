@@ -652,16 +652,20 @@ class Network(object):
     def _check_clustering(self, clustering, kmeans_init_indices, R):
         """The refusals of the clustering arguments, all before anything is uploaded.  Returns the seeds as a list of R int32 [tries, C]
         host arrays (None: to be drawn)."""
-        if clustering not in ('chunk', 'recording'):
-            raise ValueError("clustering must be 'chunk' or 'recording', got %r" % (clustering,))
+        if clustering not in ('chunk', 'recording', 'recording_soft'):
+            raise ValueError("clustering must be 'chunk' or 'recording' (or 'recording_soft' on a soft k-means model), got %r" % (clustering,))
         if clustering == 'chunk':
             if kmeans_init_indices is not None:
                 raise ValueError("kmeans_init_indices are the per-recording seeds of clustering='recording'; the per-chunk seeds of "
                                  "clustering='chunk' belong to the model (--kmeans_init_indices)")
             return None
         sep, km = self._clustering_separator()
-        if km.beta is not None:
-            raise ValueError("clustering='recording' is hard assignment only: this model runs a soft k-means (beta_kmeans = %r)" % (km.beta,))
+        if clustering == 'recording' and km.beta is not None:
+            raise ValueError("clustering='recording' is hard assignment only: this model runs a soft k-means (beta_kmeans = %r); its "
+                             "recording-level mode is clustering='recording_soft'" % (km.beta,))
+        if clustering == 'recording_soft' and km.beta is None:
+            raise ValueError("clustering='recording_soft' needs a model with a soft k-means (beta_kmeans set): this one assigns hard "
+                             "(beta_kmeans = None) and takes clustering='recording'")
         if kmeans_init_indices is None:
             return None
         seeds = list(kmeans_init_indices) if hasattr(kmeans_init_indices, '__len__') and not torch.is_tensor(kmeans_init_indices) else None
@@ -753,21 +757,25 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
-    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes, speakers=None):
+    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes, speakers=None, soft=False):
         """mix [Ctot, L]: the chunks of R recordings, counts[r] each, one after the other -> est [Ctot, S, L] with ONE k-means per
         recording over the embeddings of all its chunks.  2 ceil(Ctot / B) model passes whatever R is.  The points are held for a group
         of consecutive recordings at a time (at most cap_bytes of them); the model passes run over the WHOLE stream in the same
         batches whatever the groups are, and a recording is clustered on its own, so no result depends on the grouping.
         speakers = (lo, hi, min_score): every recording's number of clusters is chosen in lo .. hi (ams_hip/spk_count.py, DESIGN.md
-        4.11); labels below the recording's count leave the other mask columns all-zero."""
+        4.11); labels below the recording's count leave the other mask columns all-zero.
+        soft (clustering='recording_soft'): the model's soft k-means (beta_kmeans) per recording
+        (ams_hip/kmeans_ragged_soft.py); its soft labels are written straight into the [Ctot, TF, S] masks the second sweep is fed with,
+        and last_clustering holds 'masks' instead of 'labels'."""
         from ams_hip import kmeans_ragged as Kr
+        from ams_hip import kmeans_ragged_soft as Krs
         from ams_hip import spk_count as Sc
         sep, km = self._clustering_separator()
         cap = int(self.CLUSTER_CAP_BYTES if cap_bytes is None else cap_bytes)
         counts = [int(c) for c in counts]
         R, Ctot = len(counts), mix.shape[0]
         first = np.concatenate([[0], np.cumsum(counts)])
-        labels = cents = bests = None
+        labels = masks = cents = bests = None
         counted = {'counts': [], 'scores': [], 'tries': []}
         groups, g = None, 0                   # [(first recording, end recording)], the group being filled
         pts = wts = None
@@ -790,6 +798,14 @@ class Network(object):
                 for key, name in (('counts', 'count'), ('scores', 'scores'), ('tries', 'tries')):
                     counted[key].append(res[name])
                 return
+            if soft:
+                # the soft labels of the group's recordings go straight into their rows of the masks buffer
+                c, _, b = Krs.kmeans_ragged_soft(pts.view(-1, E), seg, idx, km.nb_clusters, km.nb_tries, km.nb_iterations, km.beta,
+                                                 w=None if wts is None else wts.view(-1), assign_at_end=km.assign_at_end,
+                                                 normalize_input=False, out=masks[first[r0]:first[r1]])
+                cents.append(c)
+                bests.append(b)
+                return
             c, lab, b = Kr.kmeans_ragged(pts.view(-1, E), seg, idx, km.nb_clusters, km.nb_tries, km.nb_iterations,
                                          w=None if wts is None else wts.view(-1), assign_at_end=km.assign_at_end, normalize_input=False)
             labels[first[r0]:first[r1]] = lab.view(-1, TF)
@@ -799,7 +815,11 @@ class Network(object):
         for b0, n, xn, w in self._embed_batches(mix, batch_size):
             if groups is None:
                 TF, E = xn.shape[1], xn.shape[2]
-                if speakers is None:
+                if soft:
+                    Krs.check_domain(E, km.nb_clusters, km.beta)
+                    if km.nb_clusters != self.S:
+                        raise ValueError("clustering='recording_soft': the k-means has %d clusters for %d sources" % (km.nb_clusters, self.S))
+                elif speakers is None:
                     Kr.check_domain(E, km.nb_clusters)
                 else:
                     Sc.check_range(speakers[0], speakers[1], self.S, speakers[2], E)
@@ -814,7 +834,10 @@ class Network(object):
                         r0, acc = r, 0
                     acc += c * per_chunk
                 groups.append((r0, R))
-                labels = torch.empty((Ctot, TF), dtype=torch.int32, device=xn.device)
+                if soft:
+                    masks = torch.empty((Ctot, TF, self.S), dtype=torch.float32, device=xn.device)
+                else:
+                    labels = torch.empty((Ctot, TF), dtype=torch.int32, device=xn.device)
                 cents, bests = [], []
             at = 0                           # rows of this batch handed out so far
             while at < n:
@@ -832,11 +855,11 @@ class Network(object):
                     cluster(r0, r1)
                     pts = wts = None
                     g += 1
-        self.last_clustering = {'labels': labels, 'centroids': torch.cat(cents), 'best': torch.cat(bests), 'first_chunk': first,
-                                'groups': groups}
+        self.last_clustering = {'centroids': torch.cat(cents), 'best': torch.cat(bests), 'first_chunk': first, 'groups': groups}
+        self.last_clustering['masks' if soft else 'labels'] = masks if soft else labels
         if speakers is not None:
             self.last_clustering.update({k: torch.cat(v) for k, v in counted.items()})
-        return self.infer_chunks_masked(mix, F.one_hot_masks(labels, self.S), batch_size)
+        return self.infer_chunks_masked(mix, masks if soft else F.one_hot_masks(labels, self.S), batch_size)
 
     def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
                            cluster_cap_bytes=None, speakers=None, min_score=None):
@@ -847,6 +870,11 @@ class Network(object):
         a frame in the overlap of two chunks is two points) instead of one per chunk, then the cross-fade with the identity track table:
         no border statistics, no tracker.  kmeans_init_indices: [seeds [tries, clusters]] over the recording's C TF points (default: the
         model's own draw); cluster_cap_bytes: see separate_recordings.  The default 'chunk' is the path described above, unchanged.
+
+        clustering='recording_soft' (DESIGN.md 4.13): the same for a model with a SOFT k-means (beta_kmeans set; 'recording' refuses it,
+        and this mode refuses a hard model): one soft k-means over the recording's points (ams_hip.kmeans_ragged_soft), whose soft
+        labels are the masks of every chunk.  kmeans_init_indices and cluster_cap_bytes as for 'recording'; `speakers` is not built for
+        it.  last_clustering then holds 'masks' [C, TF, S] instead of 'labels'.
 
         speakers='auto' (= (2, S)) or (lo, hi), with clustering='recording' (DESIGN.md 4.11): the number of speakers S_r of the recording
         is chosen in lo .. hi by the simplified silhouette of the k-means of every candidate count, and out is [S_r, N], the first S_r
@@ -875,9 +903,9 @@ class Network(object):
         x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
         if x.dim() != 1 or x.shape[0] < 1:
             raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
-        if clustering == 'recording':
+        if clustering != 'chunk':
             mix = St.chunks(x, L, H)
-            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes, spk)
+            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft')
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(mix.shape[0], 1)       # the identity: nothing to track
             out = St.overlap_add(est, trk, x.shape[0], H)
             return out if spk is None else out[:int(self.last_clustering['counts'][0])]
@@ -933,6 +961,10 @@ class Network(object):
         embeddings are held for a group of consecutive recordings of at most that many bytes at a time; a recording's result does not
         depend on the grouping; a single recording above the cap is refused.
 
+        clustering='recording_soft' (DESIGN.md 4.13): the same for a model with a soft k-means (beta_kmeans set): all recordings in ONE
+        ragged soft call per group (ams_hip.kmeans_ragged_soft), the soft labels written straight into the masks of the second sweep;
+        every recording is bit-equal to separate_recording on it alone with the same seeds.  Not with `speakers`.
+
         speakers / min_score as in separate_recording: every recording gets its own number of speakers S_r, chosen for all recordings in
         one counted call whose launches do not depend on len(xs), and its result is [S_r, N_r]."""
         from ams_hip import stitch as St
@@ -986,8 +1018,8 @@ class Network(object):
             for x, o, n in zip(xs, lay.x_off, lay.n):
                 host[o:o + n] = x.detach().cpu().numpy() if torch.is_tensor(x) else x
             mix = Sb.chunks_packed(torch.from_numpy(host).to(device), lay)
-        if clustering == 'recording':
-            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes, spk)
+        if clustering != 'chunk':
+            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft')
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(lay.Ctot, 1)          # the identity: nothing to track
             out = Sb.overlap_add_many(est, trk, lay)
             outs = [out[int(o):int(o) + self.S * int(n)].view(self.S, int(n)) for o, n in zip(lay.out_off, lay.n)]
