@@ -109,6 +109,94 @@ class _Overlap(object):
 OVERLAP = _Overlap()
 
 
+class _ForwardBranch(object):
+    """What a training pass needs later and that depends only on weights and inputs -- the weight images of the layers above the
+    first (W^T for their forward products, W for their dX products) and the labels with their counts -- runs on OVERLAP's side stream
+    beside the forward recurrence rings, which leave a fifth of the CUs idle, instead of in line in front of each consumer.
+    arm() (utils/ops.py::f_props) says what, in stages: beside the first layer's ring the images of the BLSTM layers above and the labels,
+    beside the second layer's ring the two images of the dense layer (a stack of one layer: everything beside its ring).  fire() forks
+    behind the layer's input projection and is issued behind the ring (ops.blstm_fwd: beside_recurrence); join() stands in front of the
+    next layer.  The cut is ONE launch of as many workgroups as the ring leaves CUs, padded so that none of them fits on a CU that holds
+    a ring workgroup (ops.beside_ring_launch): a launch that shares the ring's CUs makes the ring 25 % longer, which costs more than the
+    cuts save.  The images go where their consumers look (ops.cut_weight_images), so a product whose image was not cut here -- or a pass
+    that never armed -- cuts in line as before.  AMS_FWD_BRANCH=0: nothing is armed."""
+
+    def __init__(self):
+        import os
+        self.on = os.environ.get('AMS_FWD_BRANCH', '1') != '0'
+        self.stages = []
+        self.todo = None
+        self.event = None
+        self.fired = self.images = 0             # branches forked / weight images cut on them so far (tests, reports)
+
+    def arm(self, blstm_params, dense_params, beside=None):
+        """blstm_params: (Kf, bf, Kb, bb) of the BLSTM layers ABOVE the first, bottom up; dense_params: (W, b) of the dense layer on top
+        or None; beside: further work for the branch (the model's labels).  Armed only where OVERLAP could run (a training pass on the
+        device with gradient views)."""
+        self.stages = []
+        if not (self.on and OVERLAP.enabled and torch.is_grad_enabled()):
+            return
+        above = list(blstm_params)
+        self.stages = [(above, None if above else dense_params, beside)]
+        if above and dense_params is not None:
+            self.stages.append(([], dense_params, None))
+
+    def fire(self, x, H, forked):
+        """The next stage as a side branch.  Called twice by ops.blstm_fwd: with forked None in front of the event it records -- what
+        the stage needs of the current stream (a weight bound measured at its first use) is launched here, so the event covers it --,
+        then behind the ring with that event, on which alone the branch depends.  x [B, T, D], H: input and width of the layer whose
+        ring it runs beside (the products above have B * T rows)."""
+        if forked is None:
+            self.todo = self._prepare(x, H)
+            return
+        todo, self.todo = self.todo, None
+        if todo is None:
+            return
+        fwd, dx, beside, wgs, pad = todo
+        main = torch.cuda.current_stream()
+        s = OVERLAP.side()
+        s.wait_event(forked)
+        with torch.cuda.stream(s):
+            self.images += ops.cut_weight_images(fwd, dx, consumer=main, workgroups=wgs, lds_pad=pad)
+            self.fired += 1
+            if beside is not None:
+                for t in beside():
+                    t.record_stream(main)
+            self.event = s.record_event()
+
+    def _prepare(self, x, H):
+        layers, dense, beside = self.stages.pop(0)
+        if not x.is_cuda:
+            return None
+        M = x.shape[0] * x.shape[1]
+        fwd, dx = [], []
+        wgs, pad = ops.beside_ring_launch(x.shape[0], H)
+        for Kf, bf, Kb, bb in (layers if wgs else []):
+            aw = ops.param_amax(Kf) if ops.F16X3 else None
+            if aw is None or aw is not ops.param_amax(Kb) or not ops._twin(Kf, Kb):
+                continue                                         # (gathered kernels are a fresh copy per call: no address to key on)
+            H4 = Kf.shape[1]
+            Wcat = ops.blstm_wcat(Kf, Kb, Kf.shape[0] - H4 // 4)
+            fwd.append((M, Wcat, aw, (Kf, Kb), 'blstm_input_gemm'))
+            if OVERLAP.usable(Kf, Kb, bf, bb):                   # (else BLSTMLayer.backward takes ops.blstm_bwd: its own products)
+                dx.insert(0, (M, Wcat, aw, (Kf, Kb), ''))
+        if dense is not None and wgs:
+            W, b = dense
+            aw = ops.param_amax(W) if ops.F16X3 else None
+            if aw is not None:
+                fwd.append((M, W, aw, (W,), ''))
+                dx.insert(0, (M, W, aw, (W,), ''))
+        return fwd, dx, beside, wgs, pad
+
+    def join(self):
+        ev, self.event = self.event, None
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+
+
+FORWARD_BRANCH = _ForwardBranch()
+
+
 class FrontFilter(Function):
     """f = |w| * bases   (models/adapt.py:106, :234)."""
 
@@ -173,7 +261,9 @@ class BLSTMLayer(Function):
             aw = None
         ax = ops.amax_of(x) if aw is not None else None
         ctx.amax = (ax, aw) if aw is not None else None
-        out, G, cst = ops.blstm_fwd(x, Kf, bf, Kb, bb, amax=ctx.amax)
+        FORWARD_BRANCH.join()                                    # (the layer below forked it: its images and labels are there from here on)
+        fb = FORWARD_BRANCH
+        out, G, cst = ops.blstm_fwd(x, Kf, bf, Kb, bb, amax=ctx.amax, beside_recurrence=(lambda ev: fb.fire(x, Kf.shape[1] // 4, ev)) if fb.stages else None)
         if x.is_cuda:
             ops.tag_amax(out, ops.amax_one(out.device))          # |tanh(c) sigmoid(o)| < 1
         ctx.last_capped = bool(last_capped)
@@ -260,6 +350,7 @@ class Dense(Function):
         ctx.bias = b
         aw = ops.param_amax(W) if ops.F16X3 and x.is_cuda else None
         ctx.amax = (ops.amax_of(x), aw) if aw is not None else None         # fp16x3 products (amax_a / amax_b of the product entry points)
+        FORWARD_BRANCH.join()
         return ops.dense_fwd(x, W, b, amax=ctx.amax)
 
     @staticmethod

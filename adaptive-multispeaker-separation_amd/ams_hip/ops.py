@@ -832,14 +832,19 @@ def _ps_weight_image(W2, amax_w, owners):
     return derived(owners, 'ps_w', lambda old: (ps_pack_cols(W2, amax_w), amax_w), key=(W2.data_ptr(), W2.shape, id(amax_w)))[0]
 
 
+def _presplit_class(M, N, K, amax, label, ldc):
+    """The part of forward_product_presplit() that is known before the output exists (what cut_weight_images() asks ahead of the product)."""
+    key = ('gemm', label, M, N, K, False, False)
+    return (PRESPLIT and amax is not None and amax[0] is not None and amax[1] is not None and key not in F16_AUDIT.denied
+            and not F16_AUDIT.active and LDS_PAD[0] == 0 and N % 4 == 0 and ldc % 4 == 0
+            and max(M, N) * ((K + 31) // 32 * 128) < 2 ** 31 and load().ams_gemm_get_arith() != 0)
+
+
 def forward_product_presplit(M, N, K, out, bias, amax, label, ldc):
     """Does out[M, N] = x . W (+ bias) run from pre-split operand images?  Both operand bounds at hand, fp16x3 not denied for this
     product class, no audit in progress, no residency cap, 16-byte addressable output; K may be anything (the images pad it)."""
-    key = ('gemm', label, M, N, K, False, False)
-    return (PRESPLIT and amax is not None and amax[0] is not None and amax[1] is not None and key not in F16_AUDIT.denied
-            and not F16_AUDIT.active and LDS_PAD[0] == 0 and N % 4 == 0 and ldc % 4 == 0 and out.data_ptr() % 16 == 0
-            and (bias is None or bias.data_ptr() % 16 == 0) and max(M, N) * ((K + 31) // 32 * 128) < 2 ** 31
-            and load().ams_gemm_get_arith() != 0)
+    return (_presplit_class(M, N, K, amax, label, ldc) and out.data_ptr() % 16 == 0
+            and (bias is None or bias.data_ptr() % 16 == 0))
 
 
 def forward_product(x2, W2, bias, out, amax, label, owners, ldc=None):
@@ -870,6 +875,95 @@ def _ps_dx_weight_image(W2, amax_w, owners):
     return derived(owners, 'ps_dx', lambda old: (ps_pack_rows(W2, amax_w), amax_w), key=(W2.data_ptr(), W2.shape, id(amax_w)))[0]
 
 
+def _dx_image_class(M, N, K, amax, label):
+    """The part of backward_product()'s conditions for the image form that is known before dU exists (cut_weight_images() asks ahead)."""
+    key = ('gemm', label, M, N, K, False, True)
+    # (the last two: where the in-product form is fp16x3 -- 16-byte fetches -- on the same 128 x 256 tile, csrc/gemm.hip: launch,
+    # x6_choose_cfg, and so gives the same bits)
+    return (DX_PS and F16X3 and amax is not None and amax[0] is not None and amax[1] is not None and key not in F16_AUDIT.denied
+            and not F16_AUDIT.active and LDS_PAD[0] == 0 and N % 4 == 0 and N * ((K + 31) // 32 * 128) < 2 ** 31
+            and load().ams_gemm_get_arith() != 0 and K % 4 == 0 and (N + 255) // 256 * 256 <= 1.30 * N)
+
+
+# Several operand images from one launch (include/ams.h: ams_ps_pack_many).  AMS_PS_PACK_MANY=0: one launch per image (A/B runs).
+PACK_MANY = _os.environ.get('AMS_PS_PACK_MANY', '1') != '0'
+PS_PACK_MAX = 8
+
+
+class _PackRegion(ctypes.Structure):                             # include/ams.h: ams_ps_pack_region
+    _fields_ = [('src', ctypes.c_void_p), ('ld', ctypes.c_long), ('img', ctypes.c_void_p), ('amax', ctypes.c_void_p),
+                ('K', ctypes.c_int), ('rows', ctypes.c_int), ('kind', ctypes.c_int), ('pitch', ctypes.c_uint),
+                ('first_block', ctypes.c_uint)]
+
+
+def ps_pack_many(items, imgs=None, workgroups=0, lds_pad=0):
+    """items: [(x2, amax, 'rows' | 'cols'), ...] -> the images ps_pack_rows(x2, amax) / ps_pack_cols(x2, amax) give, eight per launch.
+    imgs: the buffers to write (else fresh ones).  workgroups: of the launch (0: one per block of the separate launches; fewer walk the
+    blocks with the grid's stride); lds_pad: bytes of dynamic LDS asked for and not used (a residency cap, as the products' lds_pad)."""
+    lib = load()
+    regs, out = [], []
+    for i, (x2, amax, kind) in enumerate(items):
+        if kind not in ('rows', 'cols'):
+            raise AmsError('ps_pack_many: kind %r' % (kind,))
+        if x2.dtype != torch.float32 or not x2.is_cuda or x2.dim() != 2 or x2.stride(1) != 1:
+            raise AmsError('ps_pack_many: fp32 device matrices with dense rows expected')
+        R, K = x2.shape if kind == 'rows' else (x2.shape[1], x2.shape[0])
+        img = imgs[i] if imgs is not None else torch.empty((R, lib.ams_ps_image_pitch(K)), dtype=torch.uint8, device=x2.device)
+        out.append(img)
+        regs.append(_PackRegion(x2.data_ptr(), x2.stride(0), img.data_ptr(), amax.data_ptr(), K, R, 0 if kind == 'rows' else 1, 0, 0))
+    for i in range(0, len(regs), PS_PACK_MAX):
+        tab = (_PackRegion * len(regs[i:i + PS_PACK_MAX]))(*regs[i:i + PS_PACK_MAX])
+        check(lib.ams_ps_pack_many(ctypes.cast(tab, ctypes.c_void_p), len(tab), int(workgroups), int(lds_pad), _s()), 'ams_ps_pack_many')
+    return out
+
+
+def cut_weight_images(forward, dx, consumer=None, workgroups=0, lds_pad=0):
+    """The weight images the rest of this pass will ask for, cut NOW on the current stream and stored where their consumers look
+    (derived(): 'ps_w' for forward_product, 'ps_dx' for backward_product, today's keys) -- one launch for all of them.
+    forward: [(M, W2 [K, N], amax_w, owners, label)] of products x [M, K] . W2;  dx: [(M, W2 [N, K], amax_w, owners, label)] of products
+    dU [M, K] . W2^T.  A product whose class does not take the image form (no bound, denied, audit in progress, residency cap) is left
+    out and keeps its in-line path; so is an image that is still valid (frozen owners).  consumer: the stream that will read the images
+    when it is not the current one; workgroups, lds_pad: of the launch (ps_pack_many).  Returns the number of images cut."""
+    one = None
+    todo = []
+
+    def want(owners, name, W2, amax_w, kind):
+        def make(old):
+            R, K = W2.shape if kind == 'rows' else (W2.shape[1], W2.shape[0])
+            img = torch.empty((R, load().ams_ps_image_pitch(K)), dtype=torch.uint8, device=W2.device)
+            if consumer is not None:
+                img.record_stream(consumer)
+            todo.append(((W2, amax_w, kind), img))
+            return (img, amax_w)
+        derived(owners, name, make, key=(W2.data_ptr(), W2.shape, id(amax_w)))
+
+    for M, W2, amax_w, owners, label in forward:
+        if amax_w is None or not W2.is_cuda or W2.stride(1) != 1:
+            continue
+        one = amax_one(W2.device) if one is None else one
+        K, N = W2.shape
+        if _presplit_class(M, N, K, (one, amax_w), label, N):
+            want(owners, 'ps_w', W2, amax_w, 'cols')
+    for M, W2, amax_w, owners, label in dx:
+        if amax_w is None or not W2.is_cuda or W2.stride(1) != 1:
+            continue
+        one = amax_one(W2.device) if one is None else one
+        N, K = W2.shape
+        if _dx_image_class(M, N, K, (one, amax_w), label):
+            want(owners, 'ps_dx', W2, amax_w, 'rows')
+    if not todo:
+        return 0
+    cur = torch.cuda.current_stream()
+    for (W2, amax_w, kind), img in todo:
+        amax_w.record_stream(cur)
+    if PACK_MANY:
+        ps_pack_many([t[0] for t in todo], imgs=[t[1] for t in todo], workgroups=workgroups, lds_pad=lds_pad)
+    else:
+        for (W2, amax_w, kind), img in todo:
+            (ps_pack_rows if kind == 'rows' else ps_pack_cols)(W2, amax_w, img=img)
+    return len(todo)
+
+
 def backward_product(dU2, W2, amax, owners, out=None, label=''):
     """out [M, N] = dU2 [M, K] . W2 [N, K]^T: the input gradients of the dense layer and of a BLSTM layer's input projection.  From a
     pre-split image of W2 (cut once per pass, kept for frozen weights) with dU2 cut inside the product where both bounds are at hand,
@@ -881,15 +975,9 @@ def backward_product(dU2, W2, amax, owners, out=None, label=''):
         out = torch.empty((M, N), dtype=torch.float32, device=dU2.device)
     ldc = out.stride(0) if out.dim() == 2 else N
     lda = dU2.stride(0)
-    key = ('gemm', label, M, N, K, False, True)
     lib = load()
-    if not (DX_PS and F16X3 and amax is not None and amax[0] is not None and amax[1] is not None and key not in F16_AUDIT.denied
-            and not F16_AUDIT.active and LDS_PAD[0] == 0 and N % 4 == 0 and ldc % 4 == 0 and lda % 4 == 0 and dU2.stride(1) == 1
-            and W2.stride(1) == 1 and out.data_ptr() % 16 == 0 and dU2.data_ptr() % 16 == 0 and M * lda * 4 < 2 ** 31
-            and N * ((K + 31) // 32 * 128) < 2 ** 31 and lib.ams_gemm_get_arith() != 0
-            and K % 4 == 0 and (N + 255) // 256 * 256 <= 1.30 * N):
-        # (the last two: where the in-product form is fp16x3 -- 16-byte fetches -- on the same 128 x 256 tile, csrc/gemm.hip: launch,
-        # x6_choose_cfg, and so gives the same bits)
+    if not (_dx_image_class(M, N, K, amax, label) and ldc % 4 == 0 and lda % 4 == 0 and dU2.stride(1) == 1
+            and W2.stride(1) == 1 and out.data_ptr() % 16 == 0 and dU2.data_ptr() % 16 == 0 and M * lda * 4 < 2 ** 31):
         return gemm(dU2, W2, transB=True, out=out, M=M, N=N, K=K, lda=lda, ldb=W2.stride(0), ldc=ldc, label=label, amax=amax)
     b_img = _ps_dx_weight_image(W2, amax[1], owners)
     nb = lib.ams_gemm_ps_a_workspace_bytes(M, N, K)
@@ -1063,10 +1151,26 @@ def _padded_rows(x2, Dp):
     return xp
 
 
-def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
+# The forward ring of a [B, T, H] layer: 2 directions x ceil(B / 16) chains of ceil(H / 12) workgroups, one per CU, 24.6 KB of LDS each
+# (DESIGN 4.2).  A launch that is to run BESIDE it without sharing a CU with it: as many workgroups as CUs are left, each padded so that
+# pad + its own 8.3 KB + the ring's 24.6 KB exceed a CU's 160 KB.
+BESIDE_RING_PAD = 128 * 1024
+
+
+def beside_ring_launch(B, H):
+    """(workgroups, dynamic-LDS pad) of a launch beside the forward ring of a layer [B, *, H]; (0, 0): the ring leaves no CU per XCD."""
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    idle = cus - 2 * ((B + 15) // 16) * ((H + 11) // 12)
+    return (idle, BESIDE_RING_PAD) if idle >= 8 else (0, 0)
+
+
+def blstm_fwd(x, Kf, bf, Kb, bb, amax=None, beside_recurrence=None):
     """One BLSTM layer (utils/ops.py:358-383).  x [B,T,D]; K* [D+H,4H]; b* [4H].
     Returns out [B,T,2H] and the tensors the backward needs (G = activated gates, cst = cell states).
-    amax: (bound of x, bound of the kernels) -> the input projection and the ring's recurrent product run as fp16x3."""
+    amax: (bound of x, bound of the kernels) -> the input projection and the ring's recurrent product run as fp16x3.
+    beside_recurrence: called with None in front of an event recorded between the input projection and the recurrence, then behind the
+    recurrence's launch with that event
+    (functional.FORWARD_BRANCH: the side branch waits for that event, not for the recurrence)."""
     _chk(x, bf, bb)
     _chk_rows(Kf, Kb)
     lib = load()
@@ -1101,15 +1205,25 @@ def blstm_fwd(x, Kf, bf, Kb, bb, amax=None):
     # ring recurrence: plane 0 = c_t (what every backward reads as `cst`), plane 1 = tanh(c_t) for the backward ring
     cst = torch.empty(((2, B, T, 2, H) if nring else (B, T, 2, H)), dtype=torch.float32, device=x.device)
     blstm_input_projection(x2, Wcat, bias, G.view(B * T, 8 * H), amax, (Kf, Kb))
+    # the branch depends on what is in the stream up to HERE and is issued BEHIND the recurrence: issued in front of it, its workgroups
+    # take the CUs first and the ring waits for them (profiles/r11_a_side_branch_ab.txt: 2.58 against 2.52 ms per step)
+    forked = None
+    if beside_recurrence is not None:
+        beside_recurrence(None)                                  # (what it needs of THIS stream goes in front of the event)
+        forked = torch.cuda.current_stream().record_event()
     if nring:
         sync, pre0 = _ring_sync(nring, x)
         check(lib.ams_blstm_ring_fwd(_p(G), _p(out), _p(cst[0]), _p(cst[1]), _p(Kf[D:]), _p(Kb[D:]), ldu,
                                      _p(u_amax if F16X3 else None), _p(sync), nring, _p(ring_error_word(x.device)), B, T, H,
                                      int(LSTM_RING == 'safe') | pre0, _s()), 'ams_blstm_ring_fwd')
+        if forked is not None:
+            beside_recurrence(forked)
         return out, G, cst
     pack = torch.empty(lib.ams_blstm_pack_floats(H, 0), dtype=torch.float32, device=x.device)
     check(lib.ams_blstm_recurrent_fwd(_p(G), _p(out), _p(cst), _p(Kf[D:]), _p(Kb[D:]), ldu, _p(pack), B, T, H, _s()),
           'ams_blstm_recurrent_fwd')
+    if forked is not None:
+        beside_recurrence(forked)
     return out, G, cst
 
 

@@ -45,10 +45,11 @@ constexpr int PS_LDS = PS_BIAS_OFF + 2 * 1024;                                  
 // ---- image writers ------------------------------------------------------------------------------------------------------------------
 // x [R, K] row-major (row pitch ldx floats) -> image rows of `pitch` bytes.  One thread per (row, group of 8 k): two float4 in, 16 B of
 // hi and 16 B of lo out; the 4 threads of a k-tile write its 64 + 64 bytes.
-__global__ __launch_bounds__(256) void ps_pack_rows_kernel(const float* __restrict__ x, long ldx, unsigned char* __restrict__ img,
-                                                           unsigned pitch, int R, int K, const float* __restrict__ amax) {
+// (`block`: the workgroup's index within this image's launch -- blockIdx.x of ps_pack_rows_kernel, a region's own count in ps_pack_many_kernel)
+__device__ __forceinline__ void ps_pack_rows_body(const float* __restrict__ x, long ldx, unsigned char* __restrict__ img,
+                                                  unsigned pitch, int R, int K, const float* __restrict__ amax, unsigned block) {
     const int groups = (int)(pitch / 32);                       // 8-k groups per image row (Kp / 8)
-    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    const long id = (long)block * 256 + threadIdx.x;
     if (id >= (long)R * groups) return;
     const int r = (int)(id / groups), gq = (int)(id - (long)r * groups), k = gq * 8;
     const float s = f16_scale(amax[0]);
@@ -71,19 +72,25 @@ __global__ __launch_bounds__(256) void ps_pack_rows_kernel(const float* __restri
     *reinterpret_cast<uint4*>(p + 64) = lo;
 }
 
+__global__ __launch_bounds__(256) void ps_pack_rows_kernel(const float* __restrict__ x, long ldx, unsigned char* __restrict__ img,
+                                                           unsigned pitch, int R, int K, const float* __restrict__ amax) {
+    ps_pack_rows_body(x, ldx, img, pitch, R, K, amax, blockIdx.x);
+}
+
 // w [K, N] row-major (row pitch ldw floats) -> image of w^T: image row n holds w[:, n] along k.  A workgroup turns 32 (k) x 64 (n) blocks
 // round in LDS, PS_PC_KT k-tiles one after another (3040 workgroups of one block each took 18 us for the 600 x 10240 dense kernel):
 // coalesced reads along n -- the next block's values are in flight while this one is cut --, then thread (n, group of 8 k) writes 16 bytes
 // of hi and of lo: a wave writes 16 image rows x 64 contiguous bytes per plane.
 constexpr int PS_PC_KT = 4;
-__global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restrict__ w, long ldw, unsigned char* __restrict__ img,
-                                                           unsigned pitch, int K, int N, const float* __restrict__ amax) {
+// (bx, by: the workgroup's place in this image's grid of 64-column blocks x groups of PS_PC_KT k-tiles)
+__device__ __forceinline__ void ps_pack_cols_body(const float* __restrict__ w, long ldw, unsigned char* __restrict__ img,
+                                                  unsigned pitch, int K, int N, const float* __restrict__ amax, unsigned bx, unsigned by) {
     __shared__ float t[32][65];
-    const int n0 = blockIdx.x * 64;
+    const int n0 = (int)bx * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int nl = threadIdx.x >> 2, kg = threadIdx.x & 3;
     const float s = f16_scale(amax[0]);
-    const int kt_end = min((int)((K + 31) / 32), (int)(blockIdx.y + 1) * PS_PC_KT);
+    const int kt_end = min((int)((K + 31) / 32), (int)(by + 1) * PS_PC_KT);
     float v[8];
     auto fetch = [&](int kt) {
 #pragma unroll
@@ -92,7 +99,7 @@ __global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restri
             v[i] = (k < K && n < N) ? w[(long)k * ldw + n] : 0.f;
         }
     };
-    int kt = blockIdx.y * PS_PC_KT;
+    int kt = (int)by * PS_PC_KT;
     if (kt < kt_end) fetch(kt);
     for (; kt < kt_end; ++kt) {
         __syncthreads();                            // the previous block has been read
@@ -109,6 +116,33 @@ __global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restri
             unsigned char* p = img + (long)(n0 + nl) * pitch + kt * 128 + kg * 16;
             *reinterpret_cast<uint4*>(p) = hi;
             *reinterpret_cast<uint4*>(p + 64) = lo;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ps_pack_cols_kernel(const float* __restrict__ w, long ldw, unsigned char* __restrict__ img,
+                                                           unsigned pitch, int K, int N, const float* __restrict__ amax) {
+    ps_pack_cols_body(w, ldw, img, pitch, K, N, amax, blockIdx.x, blockIdx.y);
+}
+
+// Several images in ONE flat launch (include/ams.h: ams_ps_pack_many): the table travels in the kernel arguments, a workgroup finds the
+// region its index falls into (first_block ascending) and runs that region's body -- the two functions above, so every image is what its
+// own launch writes.  A pass's weight images are six launches of 5 - 14 us; beside a recurrence ring that holds most of the chip each of
+// them would pay a kernel boundary of its own.
+struct PsPackTable { ams_ps_pack_region r[AMS_PS_PACK_MAX]; int n; unsigned blocks; };
+__global__ __launch_bounds__(256) void ps_pack_many_kernel(const PsPackTable tab) {
+    // (a launch of fewer workgroups than blocks -- ams_ps_pack_many's max_workgroups -- walks them with the grid's stride)
+    for (unsigned blk = blockIdx.x; blk < tab.blocks; blk += gridDim.x) {
+        int i = 0;
+#pragma unroll
+        for (int j = 1; j < AMS_PS_PACK_MAX; ++j) i += (j < tab.n && blk >= tab.r[j].first_block) ? 1 : 0;
+        const ams_ps_pack_region& g = tab.r[i];
+        const unsigned local = blk - g.first_block;
+        if (g.kind == AMS_PS_PACK_ROWS) {
+            ps_pack_rows_body(g.src, g.ld, (unsigned char*)g.img, g.pitch, g.rows, g.K, g.amax, local);
+        } else {
+            const unsigned gx = (unsigned)((g.rows + 63) / 64);
+            ps_pack_cols_body(g.src, g.ld, (unsigned char*)g.img, g.pitch, g.K, g.rows, g.amax, local % gx, local / gx);
         }
     }
 }
@@ -591,6 +625,31 @@ ams_status ams_ps_pack_cols(const float* w, long ldw, void* img, int K, int N, c
     const unsigned pitch = (unsigned)ams_ps_image_pitch(K);
     hipLaunchKernelGGL(ps_pack_cols_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)(((K + 31) / 32 + PS_PC_KT - 1) / PS_PC_KT)), dim3(256), 0, (hipStream_t)stream, w, ldw,
                        (unsigned char*)img, pitch, K, N, amax);
+    return ams_check_launch();
+}
+
+ams_status ams_ps_pack_many(const ams_ps_pack_region* regions, int n, int max_workgroups, int lds_pad, void* stream) {
+    AMS_REQUIRE(regions && n >= 1 && n <= AMS_PS_PACK_MAX && max_workgroups >= 0 && lds_pad >= 0 && lds_pad <= 150 * 1024);
+    PsPackTable tab{};
+    tab.n = n;
+    unsigned long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        ams_ps_pack_region g = regions[i];
+        AMS_REQUIRE(g.src && g.img && g.amax && g.rows > 0 && g.K > 0 && (((uintptr_t)g.img) & 15) == 0);
+        AMS_REQUIRE(g.kind == AMS_PS_PACK_ROWS || g.kind == AMS_PS_PACK_COLS);
+        AMS_REQUIRE(g.ld >= (g.kind == AMS_PS_PACK_ROWS ? g.K : g.rows));
+        g.pitch = (unsigned)ams_ps_image_pitch(g.K);
+        g.first_block = (unsigned)blocks;
+        if (g.kind == AMS_PS_PACK_ROWS) blocks += (unsigned long)(((long)g.rows * (g.pitch / 32) + 255) / 256);
+        else blocks += (unsigned long)((g.rows + 63) / 64) * (unsigned long)(((g.K + 31) / 32 + PS_PC_KT - 1) / PS_PC_KT);
+        AMS_REQUIRE(blocks < (1UL << 31));
+        tab.r[i] = g;
+    }
+    tab.blocks = (unsigned)blocks;
+    static const bool raised = [] { return hipFuncSetAttribute((const void*)ps_pack_many_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess; }();
+    if (!raised) return AMS_E_LAUNCH_FAILED;
+    const unsigned grid = (max_workgroups > 0 && (unsigned long)max_workgroups < blocks) ? (unsigned)max_workgroups : (unsigned)blocks;
+    hipLaunchKernelGGL(ps_pack_many_kernel, dim3(grid), dim3(256), (size_t)lds_pad, (hipStream_t)stream, tab);
     return ams_check_launch();
 }
 

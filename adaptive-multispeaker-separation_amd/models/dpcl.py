@@ -28,9 +28,19 @@ class DPCL(Separator):
         conv = Conv1D([1, self.layer_size, E * Fq])
         x_node = self.X
 
+        def _labels(run):
+            # the labels and their counts depend on the front output alone (network.py create_masks): beside the first forward ring
+            def make():
+                K._DPCL_AHEAD[0] = None
+                y = self.y.value(run)
+                ahead = K._DPCL_AHEAD[0]
+                return [y] + ([ahead[3]] if ahead is not None else [])
+            weighted = self.function_mask in ('linear', 'sqrt', 'square') or self.loss_with_silence
+            return make if (self.plugged and run.training and not weighted and id(self.y) not in run.cache) else None
+
         def _embed(run):
             x = x_node.value(run)
-            return conv.f_prop(f_props(layers, x, then=conv))             # [B, T, F*E]  (column = f*E + e)
+            return conv.f_prop(f_props(layers, x, then=conv, beside=_labels(run)))             # [B, T, F*E]  (column = f*E + e)
         self._embed = Node('embed', _embed, register=False)
         self._embed_normalized = True                        # prediction = l2-normalise(_embed): separate_host hands _embed to the k-means
         # Reshape + Normalize(3); only evaluated when the embeddings themselves are fetched (inference / k-means):

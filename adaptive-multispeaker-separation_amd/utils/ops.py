@@ -15,12 +15,21 @@ from ams_hip.graph import scope, get_scope_variable, get_default_graph  # noqa: 
 rng = np.random.RandomState(42)          # reference utils/ops.py:5 (module-level, shared by Conv1D inits)
 
 
-def f_props(layers, x, then=None):
-    """utils/ops.py:82-85."""
+def f_props(layers, x, then=None, beside=None):
+    """utils/ops.py:82-85.  then: the layer the caller applies to the result; beside: work of the pass that depends only on its inputs
+    (a callable returning the tensors it made).  In a training pass through a plain BLSTM stack both go to functional.FORWARD_BRANCH,
+    which runs `beside` and cuts the weight images of layers[1:] and `then` beside the first layers' recurrences."""
+    from ams_hip.graph import current_run
+    run = current_run()
+    if (run is not None and run.training and layers and all(isinstance(l, BLSTM) and l.drop_val == 0.0 for l in layers)
+            and (then is None or isinstance(then, Conv1D))):
+        F.FORWARD_BRANCH.arm([(l.Kf, l.bf, l.Kb, l.bb) for l in layers[1:]], (then.W, then.b) if then is not None else None, beside)
     for i, layer in enumerate(layers):
         if isinstance(layer, BLSTM):                 # the layer whose backward runs just before the first layer's (functional.py)
             layer._last_capped = (i == 1 and isinstance(layers[0], BLSTM))
         x = layer.f_prop(x)
+    F.FORWARD_BRANCH.stages = []                     # (a layer that did not fork its stage: nobody else may)
+    F.FORWARD_BRANCH.join()
     return x
 
 

@@ -145,6 +145,29 @@ size_t ams_ps_image_pitch(int K);
 size_t ams_ps_image_bytes(int rows, int K);
 ams_status ams_ps_pack_rows(const float* x, long ldx, void* img, int R, int K, const float* amax, void* stream);
 ams_status ams_ps_pack_cols(const float* w, long ldw, void* img, int K, int N, const float* amax, void* stream);
+/* ams_ps_pack_many (an addition within ABI 10: no earlier entry point changes): up to AMS_PS_PACK_MAX images in ONE launch -- region
+ * i is what ams_ps_pack_rows (kind AMS_PS_PACK_ROWS: src [rows, K], row pitch ld) or ams_ps_pack_cols (AMS_PS_PACK_COLS: src [K, rows],
+ * row pitch ld; image of src^T) writes for the same arguments, byte for byte; each region has its own bound.  The table is copied into
+ * the kernel's arguments; `pitch` and `first_block` are worked out by the call for its copy (what the caller puts there is ignored, the
+ * caller's table is not written).  The images must not overlap.
+ * max_workgroups: 0 = one workgroup per block of the separate launches; fewer walk the blocks with the grid's stride.  lds_pad: bytes of
+ * dynamic LDS (<= 150 KB) the launch asks for and does not use -- a residency cap, as the products' lds_pad: beside a forward recurrence
+ * ring (24.6 KB per workgroup, one per CU) a pad of 128 KB keeps every workgroup of this launch off the ring's CUs. */
+#define AMS_PS_PACK_MAX 8
+#define AMS_PS_PACK_ROWS 0
+#define AMS_PS_PACK_COLS 1
+typedef struct ams_ps_pack_region {
+    const float* src;       /* f32 matrix, dense rows */
+    long ld;                /* its row pitch in floats */
+    void* img;              /* the image, 16-byte aligned, rows x ams_ps_image_pitch(K) bytes */
+    const float* amax;      /* device pointer to the bound */
+    int K;                  /* length of an image row */
+    int rows;               /* image rows: R (rows) or N (cols) */
+    int kind;               /* AMS_PS_PACK_ROWS / AMS_PS_PACK_COLS */
+    unsigned pitch;         /* out: bytes per image row */
+    unsigned first_block;   /* out: the first workgroup of this region in the flat launch */
+} ams_ps_pack_region;
+ams_status ams_ps_pack_many(const ams_ps_pack_region* regions, int n, int max_workgroups, int lds_pad, void* stream);
 ams_status ams_gemm_ps(int M, int N, int K, const void* A_img, const void* B_img, float* C, long ldc, const float* bias,
                        const float* amax_a, const float* amax_b, void* stream);
 /* ams_gemm_ps_a_f32 (ABI 6): C[M,N] = A[M,K] . B[N,K]^T with A f32 (row pitch lda floats) and B a PS32 image -- the backward input-
