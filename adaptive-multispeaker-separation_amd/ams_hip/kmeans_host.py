@@ -189,6 +189,19 @@ class KMeans(object):
                 a[bad] = np.random.randint(0, L, size=(bad.size, C))
         return torch.from_numpy(a.astype(np.int32))
 
+    def seed_draws(self, tries, C, seed=42):
+        """uint64 [tries, C]: the random numbers one recording's k-means++ seeding consumes (ams_hip/kmeans_seed.py), from
+        a counter-based stream this object owns: splitmix64 of (seed, the number of recordings drawn for so far, try, column).  It
+        touches neither numpy's global generator nor the draw counter of the 'keyed' seeds, so the reference's seed stream stays where
+        it is, and two models built alike draw alike (tests/test_kmeans_seed_host.py pins the values)."""
+        n = np.uint64(getattr(self, '_pp_draws', 0))
+        self._pp_draws = int(n) + 1
+        t = np.arange(tries, dtype=np.uint64)[:, None]
+        c = np.arange(C, dtype=np.uint64)[None, :]
+        with np.errstate(over='ignore'):
+            base = _mix64(np.full((1, 1), seed, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + n)
+            return _mix64(_mix64(base ^ (t * np.uint64(0xD1342543DE82EF95))) + c * np.uint64(0x2545F4914F6CDD1D))
+
     def _init_idx(self, run, R, L, device):
         if self.init_indices is not None:
             v = self.init_indices.value(run) if hasattr(self.init_indices, 'value') else self.init_indices

@@ -57,6 +57,16 @@ def add_speakers_args(parser):
                         "(2 .. nb_speakers) or LO:HI (DESIGN.md 4.11); the tracks 0 .. S_r - 1 are written", required=False, default=None)
     parser.add_argument('--min_score', type=float, help='With --speakers 1:HI: the score below which a recording counts as one speaker '
                         '(no default: the criterion has not been measured on a trained model)', required=False, default=None)
+    parser.add_argument('--recording_seeding', choices=['model', 'plusplus'], default='model', help="With --clustering recording or "
+                        "recording_soft: the seeds of the recording's k-means are the model's uniform draw (default) or chosen on the GPU by "
+                        "k-means++, D^2 sampling (DESIGN.md 4.14)")
+
+
+def seeding_arg(args, whole=False):
+    """--recording_seeding, refused with SystemExit before a model is built where no recording is clustered as a whole."""
+    if args.recording_seeding == 'plusplus' and args.clustering == 'chunk' and not whole:
+        raise SystemExit('--recording_seeding plusplus goes with --clustering recording or recording_soft')
+    return args.recording_seeding
 
 
 def speakers_arg(args):
@@ -146,6 +156,7 @@ def main(argv=None):
         raise SystemExit('--sortofmodel %s: a pretraining model separates with masks made from the clean sources; a recording comes '
                          'without them' % args.sortofmodel)
     speakers = speakers_arg(args)
+    seeding = seeding_arg(args)
     fs = out_fs = None
     if args.resample:
         from ams_hip import resample
@@ -175,7 +186,7 @@ def main(argv=None):
     model = tr.prepare_inference()
     with tr.graph.as_default():
         out = model.separate_recording(x, hop=args.hop, fs=fs, output_fs=out_fs, clustering=args.clustering, speakers=speakers,
-                                       min_score=args.min_score).cpu().numpy()
+                                       min_score=args.min_score, recording_seeding=seeding).cpu().numpy()
     paths = write_outputs(args.output_prefix, out, args.input.endswith('.npy'), out_fs)
     print('\n'.join(paths))
     return paths

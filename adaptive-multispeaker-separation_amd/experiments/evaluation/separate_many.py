@@ -190,6 +190,7 @@ def main(argv=None):
     if args.speakers is not None and args.reference_dir is not None:
         raise SystemExit('--speakers with --reference_dir: scoring recordings of differing numbers of tracks is not built')
     speakers = one.speakers_arg(args)
+    seeding = one.seeding_arg(args, whole=args.score_both_clusterings)
     paths = input_paths(args)
     recs = read_all(paths, args.resample)
     refs = None if args.reference_dir is None else read_references(paths, recs, args.reference_dir, args.nb_speakers)
@@ -208,7 +209,7 @@ def main(argv=None):
     outs = [None] * len(paths)
     other = None
     counted = [None] * len(paths)                                 # with --speakers: (count, scores of the candidate counts) per input
-    spk = dict(speakers=speakers, min_score=args.min_score)
+    spk = dict(speakers=speakers, min_score=args.min_score, recording_seeding=seeding)
 
     def note(idx):
         if speakers is not None:
@@ -224,8 +225,10 @@ def main(argv=None):
             model._check_clustering(whole, None, len(recs))
             mode = whole if args.clustering == 'chunk' else 'chunk'
             xs = [x for x, _ in recs]
-            outs = [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=args.clustering)]
-            other = (mode, [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=mode)])
+            # (--recording_seeding goes to the clustering of whole recordings of the pair; 'chunk' has no such seeds)
+            how = lambda m: {} if m == 'chunk' else {'recording_seeding': seeding}          # noqa: E731
+            outs = [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=args.clustering, **how(args.clustering))]
+            other = (mode, [o.cpu().numpy() for o in model.separate_recordings(xs, hop=args.hop, clustering=mode, **how(mode))])
         elif args.resample and args.one_stream:
             res = model.separate_recordings([x for x, _ in recs], hop=args.hop, fs=[fs for _, fs in recs], output_fs=args.output_rate,
                                             clustering=args.clustering, **spk)

@@ -681,6 +681,38 @@ class Network(object):
             out.append(v.astype(np.int32))
         return out
 
+    def _check_seeding(self, clustering, recording_seeding, kmeans_seed_draws, kmeans_init_indices, R):
+        """The refusals of the seeding arguments, all before anything is uploaded.  Returns None ('model': the seeds
+        are the caller's or the model's own draw) or, for 'plusplus', a list of R entries: the caller's uint64 [tries, clusters] draws of
+        every recording, or None each where the model's KMeans is to draw them."""
+        if recording_seeding not in ('model', 'plusplus'):
+            raise ValueError("recording_seeding must be 'model' or 'plusplus', got %r" % (recording_seeding,))
+        if recording_seeding == 'model':
+            if kmeans_seed_draws is not None:
+                raise ValueError("kmeans_seed_draws are the random numbers of recording_seeding='plusplus'; the seeds of "
+                                 "recording_seeding='model' are kmeans_init_indices")
+            return None
+        if clustering == 'chunk':
+            raise ValueError("recording_seeding='plusplus' seeds the k-means of a whole recording: it needs clustering='recording' or "
+                             "'recording_soft' (the per-chunk seeds of clustering='chunk' belong to the model)")
+        if kmeans_init_indices is not None:
+            raise ValueError("recording_seeding='plusplus' chooses the seeds itself: kmeans_init_indices cannot be given with it")
+        sep, km = self._clustering_separator()
+        if kmeans_seed_draws is None:
+            return [None] * R
+        draws = list(kmeans_seed_draws) if hasattr(kmeans_seed_draws, '__len__') and not torch.is_tensor(kmeans_seed_draws) else None
+        if draws is None or len(draws) != R:
+            raise ValueError('kmeans_seed_draws: a list of one uint64 [tries, clusters] array per recording (%d), got %s'
+                             % (R, type(kmeans_seed_draws).__name__ if draws is None else 'a list of %d' % len(draws)))
+        out = []
+        for r, v in enumerate(draws):
+            v = np.asarray(v) if not torch.is_tensor(v) else None
+            if v is None or v.dtype != np.uint64 or v.shape != (km.nb_tries, km.nb_clusters):
+                raise ValueError('kmeans_seed_draws[%d] (recording %d): a host uint64 array of shape [tries, clusters] = [%d, %d], got %s'
+                                 % (r, r, km.nb_tries, km.nb_clusters, 'a tensor' if v is None else '%s %s' % (v.dtype, v.shape)))
+            out.append(np.ascontiguousarray(v))
+        return out
+
     def _chunk_batches(self, mix, batch_size, what):
         """The batches infer_chunks makes of mix [C, L]: (first chunk, chunks that count, the fed inputs) per model pass."""
         self._refuse_unless_separating()
@@ -757,7 +789,7 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
-    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes, speakers=None, soft=False):
+    def _infer_chunks_clustered(self, mix, counts, seeds, batch_size, cap_bytes, speakers=None, soft=False, plusplus=None):
         """mix [Ctot, L]: the chunks of R recordings, counts[r] each, one after the other -> est [Ctot, S, L] with ONE k-means per
         recording over the embeddings of all its chunks.  2 ceil(Ctot / B) model passes whatever R is.  The points are held for a group
         of consecutive recordings at a time (at most cap_bytes of them); the model passes run over the WHOLE stream in the same
@@ -766,9 +798,13 @@ class Network(object):
         4.11); labels below the recording's count leave the other mask columns all-zero.
         soft (clustering='recording_soft'): the model's soft k-means (beta_kmeans) per recording
         (ams_hip/kmeans_ragged_soft.py); its soft labels are written straight into the [Ctot, TF, S] masks the second sweep is fed with,
-        and last_clustering holds 'masks' instead of 'labels'."""
+        and last_clustering holds 'masks' instead of 'labels'.
+        plusplus (recording_seeding='plusplus'): per recording the uint64 [tries, S] draws, or None where the model's KMeans
+        draws them; the seeds of a group are chosen on the device from its points and the k-means' weights (ams_hip/kmeans_seed.py), copied
+        to the host ONCE per group and handed to the same calls as the seeds of the other path; last_clustering holds them as 'seeds'."""
         from ams_hip import kmeans_ragged as Kr
         from ams_hip import kmeans_ragged_soft as Krs
+        from ams_hip import kmeans_seed as Ks
         from ams_hip import spk_count as Sc
         sep, km = self._clustering_separator()
         cap = int(self.CLUSTER_CAP_BYTES if cap_bytes is None else cap_bytes)
@@ -777,6 +813,7 @@ class Network(object):
         first = np.concatenate([[0], np.cumsum(counts)])
         labels = masks = cents = bests = None
         counted = {'counts': [], 'scores': [], 'tries': []}
+        chosen = []                           # per group, the k-means++ seeds [recordings of the group, tries, S] on the device
         groups, g = None, 0                   # [(first recording, end recording)], the group being filled
         pts = wts = None
 
@@ -784,7 +821,15 @@ class Network(object):
             TF, E = pts.shape[1], pts.shape[2]
             seg = Kr.Segments([c * TF for c in counts[r0:r1]])
             # seeds per recording, in list order: the caller's, or the model's own draw (reference / fast / keyed) over the recording's points
-            idx = np.concatenate([seeds[r] if seeds is not None else km._draw(km.nb_tries, counts[r] * TF).numpy() for r in range(r0, r1)])
+            if plusplus is not None:
+                # D^2 sampling on the device, once with the model's S clusters (a count below S takes the first columns); ONE copy of
+                # R tries S int32 to the host per group, so that the calls below keep their host-side check of the seeds
+                D = np.concatenate([plusplus[r] if plusplus[r] is not None else km.seed_draws(km.nb_tries, km.nb_clusters) for r in range(r0, r1)])
+                sd = Ks.seed_plusplus(pts.view(-1, E), seg, km.nb_clusters, km.nb_tries, D, w=None if wts is None else wts.view(-1))
+                chosen.append(sd.view(r1 - r0, km.nb_tries, km.nb_clusters))
+                idx = sd.cpu().numpy()
+            else:
+                idx = np.concatenate([seeds[r] if seeds is not None else km._draw(km.nb_tries, counts[r] * TF).numpy() for r in range(r0, r1)])
             if speakers is not None:
                 lo, hi, min_score = speakers
                 res = Sc.count_clusters(pts.view(-1, E), seg, idx, lo, hi, km.nb_tries, km.nb_iterations,
@@ -823,6 +868,11 @@ class Network(object):
                     Kr.check_domain(E, km.nb_clusters)
                 else:
                     Sc.check_range(speakers[0], speakers[1], self.S, speakers[2], E)
+                if plusplus is not None:
+                    Ks.check_domain(E, km.nb_clusters)
+                    if speakers is not None and km.nb_clusters < speakers[1]:
+                        raise ValueError("recording_seeding='plusplus': the k-means has %d clusters, fewer than the %d of speakers"
+                                         % (km.nb_clusters, speakers[1]))
                 per_chunk = TF * E * 4
                 groups, r0, acc = [], 0, 0
                 for r, c in enumerate(counts):
@@ -859,10 +909,12 @@ class Network(object):
         self.last_clustering['masks' if soft else 'labels'] = masks if soft else labels
         if speakers is not None:
             self.last_clustering.update({k: torch.cat(v) for k, v in counted.items()})
+        if plusplus is not None:
+            self.last_clustering['seeds'] = torch.cat(chosen)
         return self.infer_chunks_masked(mix, masks if soft else F.one_hot_masks(labels, self.S), batch_size)
 
     def separate_recording(self, x, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
-                           cluster_cap_bytes=None, speakers=None, min_score=None):
+                           cluster_cap_bytes=None, speakers=None, min_score=None, recording_seeding='model', kmeans_seed_draws=None):
         """x [N] (a tensor or anything numpy takes) -> out [S, N] on the device: chunks of the model's chunk_size, `hop` apart (default
         half a chunk), separated by infer_chunks and put together by ams_hip.stitch (include/ams_stitch.h).
 
@@ -881,6 +933,13 @@ class Network(object):
         tracks.  lo == 1 needs min_score: the score below which the recording counts as one speaker.  last_clustering then also
         holds 'counts', 'scores' and 'tries'.  How well the criterion counts speakers on a trained model has not been measured.
 
+        recording_seeding='plusplus' (DESIGN.md 4.14), with 'recording' or 'recording_soft': the seeds of every try are chosen on the device
+        by k-means++ (D^2 sampling with integer weights, ams_hip.kmeans_seed) from the recording's points and the k-means' weights instead of
+        uniformly, copied to the host once and handed to the same k-means; with `speakers` the seeding is made once for the model's S
+        clusters and every candidate count takes its first columns.  kmeans_seed_draws: [uint64 [tries, clusters]], the random numbers
+        (default: the stream of the model's KMeans, seed_draws); not together with kmeans_init_indices.  last_clustering then also holds
+        'seeds' [1, tries, S].  The default 'model' is the path described above, every bit unchanged.
+
         fs: the sample rate of x (default config.fs, the rate the models work at).  At another rate -- or for int16 frames [N, CH], which
         are decoded and mixed down -- x is brought to config.fs on the device (ams_hip.resample, include/ams_resample.h), separated as
         above, and the [S, M] result is resampled to output_fs (default fs) and cut to ceil(N output_fs / fs) samples: N at the rate of
@@ -895,9 +954,10 @@ class Network(object):
         pcm = (x.dtype == torch.int16) if torch.is_tensor(x) else (getattr(x, 'dtype', None) == np.int16)
         seeds = self._check_clustering(clustering, kmeans_init_indices, 1)
         spk = self._check_speakers(clustering, speakers, min_score)
+        pp = self._check_seeding(clustering, recording_seeding, kmeans_seed_draws, kmeans_init_indices, 1)
         if pcm or fs_in != config.fs or fs_out != config.fs:
             return self._separate_resampled(x, pcm, H, batch_size, fs_in, fs_out, clustering, kmeans_init_indices, cluster_cap_bytes,
-                                            speakers, min_score)
+                                            speakers, min_score, recording_seeding, kmeans_seed_draws)
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(device=get_default_graph().device, dtype=torch.float32).contiguous()
@@ -905,7 +965,8 @@ class Network(object):
             raise ValueError('separate_recording: one channel of at least one sample, got %s' % (tuple(x.shape),))
         if clustering != 'chunk':
             mix = St.chunks(x, L, H)
-            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft')
+            est = self._infer_chunks_clustered(mix, [mix.shape[0]], seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft',
+                                               plusplus=pp)
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(mix.shape[0], 1)       # the identity: nothing to track
             out = St.overlap_add(est, trk, x.shape[0], H)
             return out if spk is None else out[:int(self.last_clustering['counts'][0])]
@@ -913,7 +974,7 @@ class Network(object):
         return St.stitch(est, x.shape[0], H)[0]
 
     def _separate_resampled(self, x, pcm, H, batch_size, fs_in, fs_out, clustering='chunk', kmeans_init_indices=None, cluster_cap_bytes=None,
-                            speakers=None, min_score=None):
+                            speakers=None, min_score=None, recording_seeding='model', kmeans_seed_draws=None):
         from ams_hip import resample as Rs
         Rs.ratio(fs_in, config.fs)                                 # a ValueError before anything is uploaded
         Rs.ratio(config.fs, fs_out)
@@ -928,7 +989,8 @@ class Network(object):
         N = x.shape[0]
         x = Rs.from_pcm16(x, fs_in, config.fs) if pcm else Rs.resample(x, fs_in, config.fs)
         out = self.separate_recording(x, hop=H, batch_size=batch_size, clustering=clustering, kmeans_init_indices=kmeans_init_indices,
-                                      cluster_cap_bytes=cluster_cap_bytes, speakers=speakers, min_score=min_score)
+                                      cluster_cap_bytes=cluster_cap_bytes, speakers=speakers, min_score=min_score,
+                                      recording_seeding=recording_seeding, kmeans_seed_draws=kmeans_seed_draws)
         if fs_out == config.fs:
             return out
         out = Rs.resample(out, config.fs, fs_out)
@@ -936,7 +998,7 @@ class Network(object):
         return out[:, :n_out].contiguous() if n_out < out.shape[1] else out
 
     def separate_recordings(self, xs, hop=None, batch_size=None, fs=None, output_fs=None, clustering='chunk', kmeans_init_indices=None,
-                            cluster_cap_bytes=None, speakers=None, min_score=None):
+                            cluster_cap_bytes=None, speakers=None, min_score=None, recording_seeding='model', kmeans_seed_draws=None):
         """xs: a list of recordings, float32 [N_r] each (tensors or anything numpy takes) -> a list of [S, N_r] device tensors.  The chunks
         of ALL recordings go through infer_chunks as one stream -- ceil(Ctot / batch_size) model passes instead of one or more per
         recording -- and are cut, tracked and cross-faded by kernels whose launch count does not depend on len(xs)
@@ -966,7 +1028,11 @@ class Network(object):
         every recording is bit-equal to separate_recording on it alone with the same seeds.  Not with `speakers`.
 
         speakers / min_score as in separate_recording: every recording gets its own number of speakers S_r, chosen for all recordings in
-        one counted call whose launches do not depend on len(xs), and its result is [S_r, N_r]."""
+        one counted call whose launches do not depend on len(xs), and its result is [S_r, N_r].
+
+        recording_seeding / kmeans_seed_draws as in separate_recording: one uint64 [tries, clusters] array per recording (default: drawn
+        per recording in list order); the seeds of all recordings of a group are chosen in one call whose launches do not depend on
+        len(xs), and one copy of R tries S int32 per group brings them to the host.  last_clustering['seeds'] is [R, tries, S]."""
         from ams_hip import stitch as St
         from ams_hip import stitch_batch as Sb
         self._refuse_unless_separating()
@@ -977,6 +1043,7 @@ class Network(object):
             raise ValueError('separate_recordings: an empty list of recordings')
         seeds = self._check_clustering(clustering, kmeans_init_indices, len(xs))
         spk = self._check_speakers(clustering, speakers, min_score)
+        pp = self._check_seeding(clustering, recording_seeding, kmeans_seed_draws, kmeans_init_indices, len(xs))
         L = int(self.args['chunk_size'])
         H = St.default_hop(L) if hop is None else int(hop)
         St.check_geometry(L, H)
@@ -1019,7 +1086,8 @@ class Network(object):
                 host[o:o + n] = x.detach().cpu().numpy() if torch.is_tensor(x) else x
             mix = Sb.chunks_packed(torch.from_numpy(host).to(device), lay)
         if clustering != 'chunk':
-            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft')
+            est = self._infer_chunks_clustered(mix, lay.C.tolist(), seeds, batch_size, cluster_cap_bytes, spk, soft=clustering == 'recording_soft',
+                                               plusplus=pp)
             trk = torch.arange(self.S, dtype=torch.int32, device=est.device).repeat(lay.Ctot, 1)          # the identity: nothing to track
             out = Sb.overlap_add_many(est, trk, lay)
             outs = [out[int(o):int(o) + self.S * int(n)].view(self.S, int(n)) for o, n in zip(lay.out_off, lay.n)]
