@@ -25,7 +25,15 @@ DESIGN.md 4.13).  Scoring is at the model's rate only: --reference_dir with --re
 
 With --clustering recording, --speakers auto|LO:HI (and --min_score X for LO = 1) chooses every recording's number of speakers S_r
 (DESIGN.md 4.11): D/<stem>_0 .. D/<stem>_{S_r - 1} are written, and D/counts.json holds every stem's count and the scores of its
-candidate counts.  Scoring recordings of differing numbers of tracks is not built: --speakers with --reference_dir is refused."""
+candidate counts.  Under the default metric (BSS-eval: one number of tracks for references and estimates) --speakers with
+--reference_dir is refused.
+
+With --metric si_sdr (and --reference_dir) the tracks are scored by scale-invariant SDR after the best one-to-one matching of tracks
+to true sources (utils.bss_eval.si_sdr_ragged): the true sources of an input are R/<stem>_0, _1, .. as far as they
+exist consecutively (1 .. 6: the recording's true count, whatever --nb_speakers is), a missed speaker is an unmatched reference and a
+spurious track an unmatched estimate, the mixture is the baseline of the improvement.  scores.json then carries "metric": "si_sdr",
+per recording and set the pair table, the matching, si_sdr and si_sdri per reference and the missed / spurious counts, their means
+and totals, and with --speakers the count accuracy and the confusion table true count -> counted -> n."""
 import json
 import os
 import wave
@@ -62,6 +70,9 @@ def build_parser():
     p.parser.add_argument('--score_both_clusterings', action='store_true', help="With --reference_dir: separate under 'chunk' and "
                           "under 'recording' ('recording_soft' where --clustering names it), write the tracks of the one --clustering "
                           "names, score both in the same call")
+    p.parser.add_argument('--metric', choices=['bss_eval', 'si_sdr'], default='bss_eval', help="With --reference_dir: 'bss_eval' (default: "
+                          "SDR / SIR / SAR, one number of tracks for all) or 'si_sdr': scale-invariant SDR after the best matching of "
+                          "tracks to true sources, for recordings whose numbers of tracks and of true sources differ (DESIGN.md 6d)")
     one.add_speakers_args(p.parser)
     p.add_adapt_args()
     p.add_separator_args()
@@ -85,6 +96,73 @@ def read_references(paths, recs, reference_dir, nsrc):
             rows.append(r)
         refs.append(np.stack(rows))
     return refs
+
+
+def read_references_counted(paths, recs, reference_dir, most=6):
+    """[float32 [S_r, N]] per input: <reference_dir>/<stem>_0, _1, .. as far as they exist consecutively -- the recording's true count,
+    1 .. `most`; each of the input's length; anything else is refused with the file named."""
+    refs = []
+    for p, (x, _) in zip(paths, recs):
+        stem, ext = os.path.splitext(os.path.basename(p))
+        name = lambda k: os.path.join(reference_dir, '%s_%d%s' % (stem, k, '.npy' if ext == '.npy' else '.wav'))      # noqa: E731
+        n = 0
+        while os.path.isfile(name(n)):
+            n += 1
+        if n < 1:
+            raise SystemExit('%s: the true source 0 of %s is missing' % (name(0), p))
+        if n > most:
+            raise SystemExit('%s: %s has more than %d true sources' % (name(most), p, most))
+        rows = []
+        for k in range(n):
+            r = one.read_input(name(k))
+            if r.shape[0] != x.shape[0]:
+                raise SystemExit('%s has %d samples, %s has %d: a true source has the length of its mixture' % (name(k), r.shape[0], p, x.shape[0]))
+            rows.append(r)
+        refs.append(np.stack(rows))
+    return refs
+
+
+def score_si_sdr(paths, recs, refs, sets, counted=None):
+    """sets: [(name, [tracks [S_r, N] per recording])] -> the dictionary of scores.json under --metric si_sdr.  ONE ragged call: the
+    mixture is the baseline, every set a set.  counted: with --speakers the count of every recording."""
+    from utils.bss_eval import si_sdr_ragged
+    names = [n for n, _ in sets]
+    ests = [[np.ascontiguousarray(t[i], np.float32) for _, t in sets] for i in range(len(paths))]
+    out = si_sdr_ragged(refs, ests, [np.asarray(x, np.float32) for x, _ in recs])
+    num = lambda v: [None if not np.isfinite(a) else float(a) for a in v]       # noqa: E731
+    per = []
+    pooled = {n: ([], []) for n in names}
+    for i, p in enumerate(paths):
+        Sr = int(refs[i].shape[0])
+        entry = {'input': p, 'samples': int(refs[i].shape[1]), 'references': Sr, 'info': int(out['info'][i]), 'base': num(out['base'][i, :Sr]),
+                 'sets': {}}
+        for k, name in enumerate(names):
+            Se = int(ests[i][k].shape[0])
+            entry['sets'][name] = {'tracks': Se, 'pair': [num(row[:Sr]) for row in out['pair'][i, k, :Se]],
+                                   'match_ref': [int(v) for v in out['match_ref'][i, k, :Sr]],
+                                   'match_est': [int(v) for v in out['match_est'][i, k, :Se]],
+                                   'si_sdr': num(out['si_sdr'][i, k, :Sr]), 'si_sdri': num(out['si_sdri'][i, k, :Sr]),
+                                   'missed': int(out['missed'][i, k]), 'spurious': int(out['spurious'][i, k])}
+            if out['info'][i] == 0:
+                m = out['match_ref'][i, k, :Sr] >= 0
+                pooled[name][0].extend(out['si_sdr'][i, k, :Sr][m].tolist())
+                pooled[name][1].extend(out['si_sdri'][i, k, :Sr][m].tolist())
+        per.append(entry)
+    good = out['info'] == 0
+    mean = lambda v: num([np.mean(v)])[0] if len(v) else None                   # noqa: E731
+    res = {'metric': 'si_sdr', 'zero_mean': True, 'sets': names, 'recordings': per, 'scored': int(good.sum()),
+           'means': {n: {'si_sdr': mean(pooled[n][0]), 'si_sdri': mean(pooled[n][1])} for n in names},
+           'missed': {n: int(out['missed'][good, k].sum()) for k, n in enumerate(names)},
+           'spurious': {n: int(out['spurious'][good, k].sum()) for k, n in enumerate(names)}}
+    if counted is not None:
+        true = [int(r.shape[0]) for r in refs]
+        res['count_accuracy'] = float(np.mean([c == t for c, t in zip(counted, true)]))
+        table = {}
+        for c, t in zip(counted, true):
+            row = table.setdefault(str(t), {})
+            row[str(int(c))] = row.get(str(int(c)), 0) + 1
+        res['confusion'] = table
+    return res
 
 
 def as_written(out, as_npy):
@@ -187,13 +265,23 @@ def main(argv=None):
         raise SystemExit('--score_both_clusterings goes with --reference_dir')
     if args.reference_dir is not None and args.resample:
         raise SystemExit('--reference_dir with --resample: scoring at a rate other than the model\'s %d Hz is not built' % config.fs)
-    if args.speakers is not None and args.reference_dir is not None:
-        raise SystemExit('--speakers with --reference_dir: scoring recordings of differing numbers of tracks is not built')
+    if args.metric == 'si_sdr' and args.reference_dir is None:
+        raise SystemExit('--metric si_sdr goes with --reference_dir')
+    if args.speakers is not None and args.reference_dir is not None and args.metric != 'si_sdr':
+        raise SystemExit('--speakers with --reference_dir: scoring recordings of differing numbers of tracks by BSS-eval is not built; '
+                         '--metric si_sdr scores them')
+    if args.speakers is not None and args.score_both_clusterings:
+        raise SystemExit('--speakers with --score_both_clusterings: counting under both clusterings is not built')
     speakers = one.speakers_arg(args)
     seeding = one.seeding_arg(args, whole=args.score_both_clusterings)
     paths = input_paths(args)
     recs = read_all(paths, args.resample)
-    refs = None if args.reference_dir is None else read_references(paths, recs, args.reference_dir, args.nb_speakers)
+    if args.reference_dir is None:
+        refs = None
+    elif args.metric == 'si_sdr':
+        refs = read_references_counted(paths, recs, args.reference_dir)
+    else:
+        refs = read_references(paths, recs, args.reference_dir, args.nb_speakers)
     if args.resample:
         from ams_hip import resample
         for p, (_, fs) in zip(paths, recs):
@@ -268,7 +356,10 @@ def main(argv=None):
         if other:
             sets.append((other[0], [as_written(o, n) for o, n in zip(other[1], npy)]))
             sets.sort(key=lambda s: ('chunk', 'recording', 'recording_soft').index(s[0]))
-        scores = score(paths, recs, refs, sets)
+        if args.metric == 'si_sdr':
+            scores = score_si_sdr(paths, recs, refs, sets, None if speakers is None else [c for c, _ in counted])
+        else:
+            scores = score(paths, recs, refs, sets)
         sp = os.path.join(args.output_dir, 'scores.json')
         with open(sp, 'w') as f:
             json.dump(scores, f, indent=1)

@@ -437,3 +437,25 @@ def bss_eval_sources_ragged(refs, ests, compute_permutation=True, flen=FLEN, cap
     bss_eval_sources_cupy returns."""
     crit, _ = bss_eval_pairs_ragged(refs, ests, flen=flen, cap_bytes=cap_bytes)
     return _select_all(crit, compute_permutation)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Scale-invariant SDR with rectangular matching (include/ams_sisdr.h, libams_sisdr.so; host side: ams_hip/sisdr.py): recordings of
+# ANY lengths whose numbers of references and of estimated tracks are free per recording and per set -- what BSS-eval above cannot
+# take.  Two launches per library call whatever R is.  The definition is this project's own (DESIGN.md 6d; the reference project has no
+# counterpart); its float64 restatement is tests/sisdr_ref.py.
+def si_sdr_ragged(refs, ests, mixtures, zero_mean=True, cap_bytes=None):
+    """refs[r]: [Sr_r, L_r]; ests[r]: one [Se, L_r] array or a list of K of them (one K for all recordings, 1 .. 8; Sr and Se in 1 .. 6
+    and free per recording and set); mixtures[r]: [L_r].  float32 numpy arrays or tensors; device tensors are packed on the device.
+    -> a dictionary of numpy arrays with leading axes [R, K]:
+        pair [R, K, 6, 6] (estimate, reference) si_sdr in dB, NaN outside [Se, Sr];  match_ref [R, K, 6]: the estimate of every
+        reference, match_est [R, K, 6]: the reference of every estimate, -1 for a missed reference, a spurious estimate or padding;
+        si_sdr, si_sdri [R, K, 6] per reference (NaN where unmatched; si_sdri = si_sdr - base);  missed, spurious [R, K];
+        base [R, 6] = si_sdr(mixture, reference);  info [R]: bit 0 = a silent reference (no matching, leave it out of every mean).
+    One library call per group of consecutive recordings that stays under cap_bytes (default ams_hip.sisdr.CAP_BYTES); no result
+    depends on the grouping or on the other recordings; a single recording above the cap is refused.  No CPU fallback."""
+    from ams_hip import sisdr
+    try:
+        return sisdr.si_sdr_ragged(refs, ests, mixtures, zero_mean=zero_mean, cap_bytes=cap_bytes)
+    except sisdr.SisdrError as e:
+        raise BssError(str(e))
