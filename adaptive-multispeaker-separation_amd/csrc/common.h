@@ -32,9 +32,12 @@ size_t conv_maxpool_ps_bytes(int Bt, int L, int W, int N);
 bool conv_maxpool_ps_applies(int Bt, int L, int W, int N);
 ams_status conv_maxpool_ps(const float* x, const float* f, float* pmax, int32_t* pidx, int Bt, int L, int W, int N, int pl,
                            const float* amax_x, const float* amax_f, void* img, hipStream_t st);
-// csrc/gemm.hip, used by csrc/gemm_ps.hip (ams_gemm_ps_a_f32): the k-split the in-product form's 128 x 256 tile takes for the same
-// product (cost model, k per split in *kps) and the slab reduce it runs -- the same partition and summation order, so the same bits
-int dx_splits(int M, int N, int K, size_t ws_bytes, int* kps);
+// csrc/gemm.hip, used by csrc/gemm_ps.hip (ams_gemm_ps_a_f32) AND by the in-product form's launch() for the same product class
+// (uncapped fp16x3 on the 128 x 256 configuration, B given as [N, K]): ONE rule for the k-partition of a dX product -- the cost model
+// over the image form's two tiles (128 x 256, 128 x 320) -- and the slab reduce both run: the same partition and summation order, so
+// the same bits.  tile_n is the image form's tile width; the in-product form keeps its 128 x 256 tile and follows splits / kps only.
+struct DxPlan { int tile_n, splits, kps; };
+DxPlan dx_plan(int M, int N, int K, size_t ws_bytes);
 ams_status splitk_reduce(const float* partial, float* C, int M, int N, long ldc, int splits, hipStream_t st);
 // csrc/gemm.hip, used by csrc/conv2d.hip: the dilated conv2d products as implicit GEMMs (A_CONV / A_CONV_T loaders)
 ams_status conv_fwd_or_dx(const float* x, const float* w, const float* bias, float* y, int M, int N, int T, int F, int lc, int kh, int kw,

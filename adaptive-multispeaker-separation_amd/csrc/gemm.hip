@@ -39,15 +39,18 @@ constexpr size_t AMS_SK_SLOT_BYTES = (128 * 256 + 256) * sizeof(float);     // t
 std::atomic<int> g_gemm_arith{-1};        // -1: not chosen yet (AMS_GEMM_X6, default 1), 0: native f32 MFMA, 1: bf16x6
 
 // Tuning overrides (A/B runs only): read from the environment ONCE per process, never on the launch path.
-struct GemmTuning { int group_m, splits, x6cfg, sk; bool novec, f16x3; };
+struct GemmTuning { int group_m, splits, x6cfg, sk; bool novec, f16x3; int dx_tile; };
 inline const GemmTuning& tuning() {
     static const GemmTuning t = [] {
-        GemmTuning v{0, 0, -1, 1, false, true};
+        GemmTuning v{0, 0, -1, 1, false, true, 0};
         if (const char* f = getenv("AMS_GEMM_SK")) v.sk = atoi(f);        // stream-K: 0 off, 1 the tail of multi-round launches where the cost model prefers it (default), 2 wherever it applies
         if (const char* f = getenv("AMS_GEMM_GROUP_M")) v.group_m = atoi(f);
         if (const char* f = getenv("AMS_GEMM_SPLITS")) v.splits = atoi(f);
         { const char* e = getenv("AMS_GEMM_F16X3"); v.f16x3 = !(e && atoi(e) == 0); }
         v.novec = getenv("AMS_GEMM_NOVEC") != nullptr;
+        // the dX products' plan (ams_detail::dx_plan): 256 = the 128 x 256 tile and its own slab rule for BOTH forms (the plan before the
+        // 128 x 320 instance: A/B arm and escape hatch), 320 = that instance wherever its slabs fit, else the model's choice
+        if (const char* f = getenv("AMS_GEMM_DX_TILE")) { const int c = atoi(f); if (c == 256 || c == 320) v.dx_tile = c; }
         if (const char* f = getenv("AMS_GEMM_X6CFG")) { const int c = atoi(f); if (c == 0 || c == 3) v.x6cfg = c; }     // force one bf16x6 tile configuration (X6Cfg)
         return v;
     }();
@@ -1597,8 +1600,12 @@ ams_status launch(GemmArgs& g, const LaunchOpt& opt, void* ws, size_t ws_bytes, 
     const bool whole = opt.amax_out || g.relu || g.emask;            // epilogues that need the whole k range in one workgroup
     if (ws && !whole) {
         splits = choose_splits(g.M, g.N, g.K, nbatch, tp, &t_split);
-        if (tuning().splits > 0) splits = tuning().splits;
-        while (splits > 1 && (size_t)nbatch * splits * g.M * g.N * sizeof(float) > ws_bytes) --splits;
+        // the dX product class takes its k-partition from the rule it shares with the image form (ams_gemm_ps_a_f32 gives the same bits)
+        if (AMODE == A_ROW && BKcc && f16 && cfg == 3 && !capped && nbatch == 1) splits = ams_detail::dx_plan(g.M, g.N, g.K, ws_bytes).splits;
+        else {
+            if (tuning().splits > 0) splits = tuning().splits;
+            while (splits > 1 && (size_t)nbatch * splits * g.M * g.N * sizeof(float) > ws_bytes) --splits;
+        }
     } else choose_splits(g.M, g.N, g.K, nbatch, tp, &t_split, 1);
     // workgroups of this variant a CU holds: 8-wave configurations 1; 128 x 128: 2 by registers, a residency cap may ask for 1
     int wgcu = 1;
@@ -1719,14 +1726,28 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 namespace ams_detail {
 
-// what launch() does for an uncapped fp16x3 launch on the 128 x 256 configuration (X6Cfg<3>) with ws_bytes of slabs
-__attribute__((visibility("hidden"))) int dx_splits(int M, int N, int K, size_t ws_bytes, int* kps) {
-    int splits = choose_splits(M, N, K, 1, x6_plan(3));
+// Tile and k-partition of a dX product dU [M, K] . W [N, K]^T with ws_bytes of slabs (csrc/common.h).  Two candidates under the model
+// of choose_splits_tiles: the 128 x 256 tile (what an uncapped fp16x3 launch on X6Cfg<3> took before there was a choice) and the image
+// form's 128 x 320 tile (csrc/gemm_ps.hip: gemm_ps_a320_kernel), whose cost per 16 k and workgroup is AMS_GEMM_PS320_US16 -- the
+// 256 tile's figure times the MEASURED ratio of their k-tile times: standalone at 5120 x 600 x {10240, 2400}, launch + reduce, the 256
+// tile takes 218.5 and 67.2 us for 160 and 38 k-tiles per workgroup = 1.24 us per k-tile, the 320 tile 189.5 and 62.4 us for 107 and 25
+// = 1.55 us (profiles/r12_a_dx_tile_ab.txt): 1.25, which is also the ratio of their MFMA counts.  The wider tile is taken where the
+// model says it is faster and all its slabs fit the workspace; a tie keeps the 256 tile.
+#ifndef AMS_GEMM_PS320_US16
+#define AMS_GEMM_PS320_US16 (AMS_GEMM_X6_US16_2 * 1.25)
+#endif
+__attribute__((visibility("hidden"))) DxPlan dx_plan(int M, int N, int K, size_t ws_bytes) {
+    double t256 = 1e30, t320 = 1e30;
+    int tile = 256, splits = choose_splits(M, N, K, 1, x6_plan(3), &t256);
+    if (tuning().dx_tile != 256) {
+        const TilePlan p320 = {128, 320, X6_BK, AMS_GEMM_PS320_US16, true};
+        const int s320 = choose_splits(M, N, K, 1, p320, &t320);
+        if ((tuning().dx_tile == 320 || t320 < t256) && slab_bytes(M, N, 1, s320) <= ws_bytes) { tile = 320; splits = s320; }
+    }
     if (tuning().splits > 0) splits = tuning().splits;
     while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
-    int k = ceil_div(ceil_div(K, splits), X6_BK) * X6_BK;
-    *kps = k;
-    return ceil_div(K, k);
+    const int k = ceil_div(ceil_div(K, splits), X6_BK) * X6_BK;
+    return {tile, ceil_div(K, k), k};
 }
 
 // C = sum of the slabs partial[s] [M, N] in split order (N, ldc multiples of 4, 16-byte aligned C / partial)
@@ -1793,6 +1814,12 @@ size_t ams_gemm_workspace_bytes(int M, int N, int K, int nbatch, int lds_pad) {
     if (M <= 0 || N <= 0 || K <= 0 || nbatch <= 0) return 0;
     int splits = choose_splits(M, N, K, nbatch);
     if (tuning().splits > 0) splits = tuning().splits;
+    // (a dX product on the 128 x 256 configuration follows ams_detail::dx_plan, which may ask for more slabs; this query does not know
+    // the operand forms, so every product of such a shape is lent that much)
+    if (nbatch == 1 && use_x6() && x6_choose_cfg(M, N) == 3) {
+        const int s = ams_detail::dx_plan(M, N, K, ~(size_t)0).splits;
+        if (s > splits) splits = s;
+    }
     return slab_bytes(M, N, nbatch, splits);
 }
 

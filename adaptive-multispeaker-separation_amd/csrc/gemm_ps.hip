@@ -597,6 +597,251 @@ __global__ __launch_bounds__(PS_NT, 1) void gemm_ps_kernel(const PsArgs g) {
     }
 }
 
+// ---- the mixed form on a 128 x 320 tile ------------------------------------------------------------------------------------------------
+// The dX products of the step have N = 600: three 256-column tiles cover 768 columns (22 % zeros in every workgroup's MFMAs), two
+// 320-column tiles cover 640 (6 %).  40 x 2 tiles x 3 k-slabs are the same 240 workgroups as 40 x 3 x 2, each with 40 / 3 instead of
+// 32 / 2 MFMA blocks x K: 0.83 of the work of the one round the launch is.  AF32 only: three whole stages of 56 KB do not fit a CU.
+//
+// Operands arrive as in gemm_ps_kernel<false, true>: A by two hand-counted buffer loads per thread one k-tile ahead, cut between MFMA
+// groups into swizzled 128-byte rows; B by LDS-DMA two k-tiles ahead.  What differs:
+//   waves   4 row groups x 2 column groups of 32 x 160 = 1 x 5 MFMA blocks (a 64 x 80 wave tile is no multiple of 32)
+//   LDS     A and B in rings of their own: A(t + 1) is written while t is read -> 2 stages of 16 KB; B(t + 2) lands while t and t + 1
+//           wait -> 3 stages of 40 KB; 152 KB.  A's stage (t + 1) & 1 was last read at t - 1, B's stage (t + 2) % 3 too, and every
+//           wave has left k-tile t - 1 (lgkmcnt(0)) before the barrier of t.
+//   DMA     320 B rows = 40 piece loads per k-tile, 5 per wave: wave w moves rows 40 w .. 40 w + 39
+//   wait    the VMEM operations of a wave go out in the order ... A(t + 1) [2 loads], B(t + 1) [5 DMAs] | A(t + 2) [2], B(t + 2) [5] ...
+//           (prologue: B(0) [5], A(1) [2], B(1) [5]).  At the top of k-tile t the youngest are the 5 DMAs of B(t + 1), which may stay
+//           in flight; everything older -- A(t + 1), which is cut during t, and B(t) -- must have landed: vmcnt(5).  The last k-tile
+//           has nothing younger: vmcnt(0).
+//   regs    two accumulator sets x 5 blocks = 160; fragments of ONE k-step (a hi, a lo, 5 b hi, 5 b lo = 48) live at a time: those
+//           of k-step 1 are read into the registers k-step 0 frees, one MFMA group ahead of their use
+//   order   per output element and accumulator set as in the 128 x 256 instance: cross set  lo.hi, hi.lo of k-step 0, then of
+//           k-step 1; main set  hi.hi of k-step 0, then 1.  (The two sets are separate registers: issuing hi.hi of a k-step before
+//           its hi.lo, as here, changes no sum.)  Scale, cut and (acc + accs) * sc_inv are shared code: for an equal k-partition the
+//           same bits as the 128 x 256 instance and the in-product form.
+//   stores  a wave turns its band round one 32 x 32 block at a time in a private 4 KB patch of the freed B stages
+constexpr int PW_BN = 320, PW_NB = 5;
+constexpr int PW_A_STAGE = PS_BM * 128, PW_B_STAGE = PW_BN * 128;                                          // 16 KB, 40 KB
+constexpr int PW_B_OFF = 2 * PW_A_STAGE, PW_LDS = PW_B_OFF + 3 * PW_B_STAGE;                                // 152 KB
+static_assert(PW_LDS <= 160 * 1024 && 8 * 4096 <= 3 * PW_B_STAGE, "stages and epilogue patches fit the CU's LDS");
+
+__global__ __launch_bounds__(PS_NT, 1) void gemm_ps_a320_kernel(const PsArgs g) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char ps_smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l31 = lane & 31, lk = lane >> 5;
+    int nk = 0;
+    const int n_items = g.tiles_m * g.tiles_n * g.splits, G = (int)gridDim.x;
+    const int n_work = (n_items - (int)blockIdx.x + G - 1) / G;
+    if (n_work <= 0) return;
+    __builtin_amdgcn_s_setprio(2);
+
+    auto rsrc = [](const unsigned char* p, long bytes) {
+        const unsigned long long a = (unsigned long long)(uintptr_t)p;
+        i32x4_t r = {(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
+        r.x = __builtin_amdgcn_readfirstlane(r.x); r.y = __builtin_amdgcn_readfirstlane(r.y);
+        r.z = __builtin_amdgcn_readfirstlane(r.z); r.w = __builtin_amdgcn_readfirstlane(r.w);
+        return r;
+    };
+    const i32x4_t rsA = rsrc(reinterpret_cast<const unsigned char*>(g.Af), (long)g.M * g.lda * 4), rsB = rsrc(g.B, (long)g.N * g.pitch_b);
+
+    // DMA roles: piece load q (0 .. 4) of wave w fills the B rows 40 w + 8 q + (lane >> 3) of the tile, LDS slot lane & 7 of each, from
+    // source piece slot ^ f(row), f(row) = (row >> 1) & 7 (the swizzle of gemm_ps_kernel)
+    // (the offsets are those of tile column 0 here; setup() moves them by the tile's columns, so nothing but they stays live for it)
+    const int drow = lane >> 3, dslot = lane & 7;
+    unsigned voffB[PW_NB];
+#pragma unroll
+    for (int q = 0; q < PW_NB; ++q) {
+        const int row = (PW_NB * wave + q) * 8 + drow;
+        voffB[q] = (unsigned)row * g.pitch_b + (unsigned)(dslot ^ ((row >> 1) & 7)) * 16u;
+    }
+
+    // fragment addresses inside a 32-row block of a stage: l31 * 128 + 16 * ((lk + 2 ks + 4 p) ^ f(row)), f(row) = (l31 >> 1) & 7 for
+    // every block -- four lane constants (k-step ks, plane p: 0 = hi, 1 = lo); the block (4 KB apart) is an immediate offset of the read
+    const int ff = (l31 >> 1) & 7;
+    unsigned fx[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) fx[ks][p] = (unsigned)(l31 * 128 + (((lk + 2 * ks + 4 * p) ^ ff) * 16));
+
+    const float sc_inv = (1.0f / f16_scale(g.amax_a[0])) * (1.0f / f16_scale(g.amax_b[0]));
+    const float sc_a = f16_scale(g.amax_a[0]);
+
+    int tile_m, tile_n, m0 = 0, n0 = 0, split = 0, kt0 = 0, kend = g.K;
+    const int ar = tid >> 2, ag = tid & 3, af = (ar >> 1) & 7;       // cut roles, as gemm_ps_kernel<false, true>
+    unsigned avoff = 0;
+    f32x4 ra0 = {}, ra1 = {};
+    auto setup = [&](int i) {
+        ps_locate<true>(g, (int)blockIdx.x + i * G, tile_m, tile_n, split);
+        const unsigned dn = (unsigned)(tile_n * PW_BN - n0) * g.pitch_b;       // (unsigned arithmetic: a move back wraps to the same sum)
+        m0 = tile_m * PS_BM; n0 = tile_n * PW_BN;
+        kt0 = split * (g.kps / PS_BK);
+        kend = min(g.K, (split + 1) * g.kps);
+        nk = (kend - kt0 * PS_BK + PS_BK - 1) / PS_BK;
+        int t = tid;
+        asm volatile("" : "+v"(t));                 // row and k group worked out again per item, not held in registers across the main loop
+        avoff = (m0 + (t >> 2) < g.M) ? (unsigned)((long)(m0 + (t >> 2)) * g.lda * 4) + (unsigned)(t & 3) * 32u : 0x80000000u;
+#pragma unroll
+        for (int q = 0; q < PW_NB; ++q) voffB[q] += dn;                        // rows past N: beyond num_records -> zeros
+    };
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_void*)ps_smem;
+    auto issue_b = [&](int kt, int stage, int q) {
+        const unsigned ld = lds0 + (unsigned)(PW_B_OFF + stage * PW_B_STAGE + (PW_NB * wave + q) * 1024);
+        const int ko = (kt0 + kt) * 128;
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "s"(ld), "v"(voffB[q]), "s"(rsB), "s"(ko) : "memory");
+    };
+    auto load_a = [&](int kt) {
+        const unsigned vo = avoff + (unsigned)((kt0 + kt) * 128);
+        asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %2, %3, 0 offen\n\tbuffer_load_dwordx4 %1, %2, %3, 0 offen offset:16"
+                     : "=&v"(ra0), "=&v"(ra1) : "v"(vo), "s"(rsA) : "memory");
+    };
+    auto cut_a = [&](int kt, int stage) {
+        float v[8] = {ra0[0], ra0[1], ra0[2], ra0[3], ra1[0], ra1[1], ra1[2], ra1[3]};
+        const int kb = (kt0 + kt) * PS_BK;
+        if (kb + PS_BK > kend) {                                    // (workgroup-uniform: the split's last k-tile)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (kb + ag * 8 + j < kend) ? v[j] : 0.f;
+        }
+        uint4 hi, lo;
+        split2h(v[0] * sc_a, v[1] * sc_a, hi.x, lo.x);
+        split2h(v[2] * sc_a, v[3] * sc_a, hi.y, lo.y);
+        split2h(v[4] * sc_a, v[5] * sc_a, hi.z, lo.z);
+        split2h(v[6] * sc_a, v[7] * sc_a, hi.w, lo.w);
+        unsigned char* const p = ps_smem + stage * PW_A_STAGE + ar * 128;
+        *reinterpret_cast<uint4*>(p + ((ag ^ af) * 16)) = hi;
+        *reinterpret_cast<uint4*>(p + (((4 + ag) ^ af) * 16)) = lo;
+    };
+
+    f32x16 acc[PW_NB], accs[PW_NB];
+    auto group = [&](f32x16 (&c)[PW_NB], const f16x8_t& a, const f16x8_t (&b)[PW_NB]) {
+#pragma unroll
+        for (int j = 0; j < PW_NB; ++j) c[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b[j], c[j], 0, 0, 0);
+#if AMS_PS_SLEEP
+        __builtin_amdgcn_s_sleep(AMS_PS_SLEEP);
+#endif
+    };
+    // One k-tile on A stage sa / B stage sb: 6 groups of 5 MFMAs.  PRE: A of k-tile kt2 into the staging registers and B of kt2 into
+    // stage sb2, a piece load between the groups; CUT: A of kt2 - 1 (loaded one k-tile ago) into A stage sa_c
+    auto mfma_tile = [&](int sa, int sb, auto PRE, int kt2, int sb2, auto CUT, int sa_c) {
+        constexpr bool pre = decltype(PRE)::value, cut = decltype(CUT)::value;
+        const unsigned char* const pa = ps_smem + sa * PW_A_STAGE + wm * 4096;
+        const unsigned char* const pb = ps_smem + PW_B_OFF + sb * PW_B_STAGE + wn * (PW_NB * 4096);
+        auto rd_a = [&](int ks, int p) { return *reinterpret_cast<const f16x8_t*>(pa + fx[ks][p]); };
+        auto rd_b = [&](f16x8_t (&b)[PW_NB], int ks, int p) {
+            const unsigned char* const q = pb + fx[ks][p];
+#pragma unroll
+            for (int j = 0; j < PW_NB; ++j) b[j] = *reinterpret_cast<const f16x8_t*>(q + j * 4096);
+        };
+        f16x8_t ah0, al0, ah1, al1, bh0[PW_NB], bl0[PW_NB], bh1[PW_NB], bl1[PW_NB];
+        al0 = rd_a(0, 1);
+        rd_b(bh0, 0, 0);
+        ah0 = rd_a(0, 0);
+        rd_b(bl0, 0, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        group(accs, al0, bh0);                          // k-step 0: lo . hi
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (cut) cut_a(kt2 - 1, sa_c);
+        if constexpr (pre) load_a(kt2);
+        __builtin_amdgcn_sched_barrier(0);
+        group(acc, ah0, bh0);                           // k-step 0: hi . hi (main set)
+        __builtin_amdgcn_sched_barrier(0);
+        al1 = rd_a(1, 1);                               // (into what a lo, b hi of k-step 0 leave)
+        rd_b(bh1, 1, 0);
+        if constexpr (pre) issue_b(kt2, sb2, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        group(accs, ah0, bl0);                          // k-step 0: hi . lo
+        __builtin_amdgcn_sched_barrier(0);
+        ah1 = rd_a(1, 0);                               // (into what a hi, b lo of k-step 0 leave)
+        rd_b(bl1, 1, 1);
+        if constexpr (pre) issue_b(kt2, sb2, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        group(accs, al1, bh1);                          // k-step 1: lo . hi
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (pre) issue_b(kt2, sb2, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        group(acc, ah1, bh1);                           // k-step 1: hi . hi (main set)
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (pre) { issue_b(kt2, sb2, 3); issue_b(kt2, sb2, 4); }
+        __builtin_amdgcn_sched_barrier(0);
+        group(accs, ah1, bl1);                          // k-step 1: hi . lo
+    };
+
+    // prologue of an item: A of k-tile 0 loaded and cut in line, B of k-tile 0, then A and B of k-tile 1 in flight
+    auto start = [&]() {
+        load_a(0);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+        cut_a(0, 0);
+#pragma unroll
+        for (int q = 0; q < PW_NB; ++q) issue_b(0, 0, q);
+        if (nk > 1) {
+            load_a(1);
+#pragma unroll
+            for (int q = 0; q < PW_NB; ++q) issue_b(1, 1, q);
+        }
+    };
+    setup(0);
+    start();
+    for (int wi = 0; wi < n_work; ++wi) {
+        PS_STAMP(0);
+#pragma unroll
+        for (int j = 0; j < PW_NB; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; accs[j][r] = 0.f; }
+        int sa = 0, sb = 0;
+        for (int kt = 0; kt < nk - 2; ++kt) {
+            // vmcnt(5): see "wait" above; lgkmcnt(0): this wave's cut of A(kt) is in LDS and its reads of k-tile kt - 1 are done
+            asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+            __builtin_amdgcn_s_barrier();
+            mfma_tile(sa, sb, std::true_type{}, kt + 2, sb == 0 ? 2 : sb - 1, std::true_type{}, sa ^ 1);
+            sa ^= 1; sb = sb == 2 ? 0 : sb + 1;
+        }
+        if (nk >= 2) {
+            asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" : "+v"(ra0), "+v"(ra1) :: "memory");
+            __builtin_amdgcn_s_barrier();
+            mfma_tile(sa, sb, std::false_type{}, nk, 0, std::true_type{}, sa ^ 1);
+            sa ^= 1; sb = sb == 2 ? 0 : sb + 1;
+        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        mfma_tile(sa, sb, std::false_type{}, 0, 0, std::false_type{}, 0);
+        PS_STAMP(1);
+        const bool more = wi + 1 < n_work;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                   // every wave has read its last fragments: all stages are free
+        // Epilogue (C/D layout of a 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)): block by block through the
+        // wave's patch, float4 rows out (8 lanes a row of 128 bytes)
+        float* const wl = reinterpret_cast<float*>(ps_smem + PW_B_OFF) + wave * 1024;
+        const int rr = lane >> 3, c4 = (lane & 7) * 4;
+        float* const out = g.splits > 1 ? g.partial + (long)split * g.M * g.N : g.C;
+        const long ldo = g.splits > 1 ? (long)g.N : g.ldc;
+#pragma unroll
+        for (int j = 0; j < PW_NB; ++j) {
+            acc[j] = (acc[j] + accs[j]) * sc_inv;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) wl[((r & 3) + 8 * (r >> 2) + 4 * lk) * 32 + l31] = acc[j][r];
+            const int col = n0 + (wn * PW_NB + j) * 32 + c4;
+#pragma unroll
+            for (int p4 = 0; p4 < 4; ++p4) {
+                const int rl = p4 * 8 + rr;
+                const float4 v = *reinterpret_cast<const float4*>(wl + rl * 32 + c4);
+                const int row = m0 + wm * 32 + rl;
+                if (row < g.M && col < g.N) *reinterpret_cast<float4*>(out + (long)row * ldo + col) = v;
+            }
+        }
+        PS_STAMP(2);
+        if (more) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();               // the patches have been read: the B stages may be filled
+            setup(wi + 1);
+            start();
+        }
+    }
+}
+
 inline int ps_group_m(int tiles_m, int tiles_n) {
     // band height of the XCD-aware order: an XCD's 32 concurrent tiles should be about 8 tile rows x 4 tile columns
     int gm = 8;
@@ -676,9 +921,15 @@ ams_status ams_gemm_ps(int M, int N, int K, const void* A_img, const void* B_img
 
 size_t ams_gemm_ps_a_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    int kps = 0;
-    const int splits = ams_detail::dx_splits(M, N, K, ~(size_t)0, &kps);
+    const int splits = ams_detail::dx_plan(M, N, K, ~(size_t)0).splits;
     return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
+}
+
+ams_status ams_gemm_ps_a_plan(int M, int N, int K, size_t ws_bytes, int* tile_n, int* splits, int* kps) {
+    AMS_REQUIRE(M > 0 && N > 0 && K > 0 && tile_n && splits && kps);
+    const ams_detail::DxPlan p = ams_detail::dx_plan(M, N, K, ws_bytes);
+    *tile_n = p.tile_n; *splits = p.splits; *kps = p.kps;
+    return AMS_OK;
 }
 
 ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, const void* B_img, float* C, long ldc, const float* amax_a,
@@ -691,17 +942,24 @@ ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, cons
     g.M = M; g.N = N; g.K = K; g.ldc = ldc;
     g.pitch_b = (unsigned)ams_ps_image_pitch(K);
     AMS_REQUIRE((long)M * lda * 4 < (1L << 31) && (long)N * g.pitch_b < (1L << 31));            // 32-bit buffer offsets
-    g.splits = ams_detail::dx_splits(M, N, K, ws ? ws_bytes : 0, &g.kps);
+    const ams_detail::DxPlan plan = ams_detail::dx_plan(M, N, K, ws ? ws_bytes : 0);
+    const bool wide = plan.tile_n == PW_BN;
+    AMS_REQUIRE(!wide || (long)(N + PW_BN) * g.pitch_b < (1L << 32));                           // (rows of the last tile past N)
+    g.splits = plan.splits; g.kps = plan.kps;
     g.partial = (float*)ws;
-    g.tiles_m = (M + PS_BM - 1) / PS_BM; g.tiles_n = (N + PS_BN - 1) / PS_BN;
+    g.tiles_m = (M + PS_BM - 1) / PS_BM; g.tiles_n = (N + plan.tile_n - 1) / plan.tile_n;
     g.group_m = ps_group_m(g.tiles_m, g.tiles_n);
     static const int cus = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256; return n; }();
-    static const bool raised = [] { return hipFuncSetAttribute((const void*)gemm_ps_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS) == hipSuccess; }();
+    static const bool raised = [] {
+        return hipFuncSetAttribute((const void*)gemm_ps_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS) == hipSuccess &&
+               hipFuncSetAttribute((const void*)gemm_ps_a320_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS) == hipSuccess;
+    }();
     if (!raised) return AMS_E_LAUNCH_FAILED;
     const int items = g.tiles_m * g.tiles_n * g.splits;
     int grid = items < cus ? items : cus;
     if (grid >= 8) grid -= grid % 8;
-    hipLaunchKernelGGL((gemm_ps_kernel<false, true>), dim3((unsigned)grid), dim3(PS_NT), PS_LDS, (hipStream_t)stream, g);
+    if (wide) hipLaunchKernelGGL(gemm_ps_a320_kernel, dim3((unsigned)grid), dim3(PS_NT), PW_LDS, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL((gemm_ps_kernel<false, true>), dim3((unsigned)grid), dim3(PS_NT), PS_LDS, (hipStream_t)stream, g);
     ams_status r = ams_check_launch();
     if (r == AMS_OK && g.splits > 1) r = ams_detail::splitk_reduce(g.partial, C, M, N, ldc, g.splits, (hipStream_t)stream);
     return r;

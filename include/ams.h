@@ -22,7 +22,8 @@
  *                              bounds: bf16x6), AMS_GEMM_SK (stream-K 0/1/2), AMS_GEMM_X6CFG (force tile configuration 0 or 3),
  *                              AMS_GEMM_SPLITS, AMS_GEMM_GROUP_M (split-K / band height overrides), AMS_GEMM_NOVEC (force the dword-fetch
  *                              f32 kernel), AMS_MAXPOOL_PS (0 = path B's product cuts its operands in the kernel also where the pre-split
- *                              form applies)
+ *                              form applies), AMS_GEMM_DX_TILE (256 = the dX products' plan before the 128 x 320 tile, for both forms;
+ *                              320 = that tile wherever its slabs fit: ams_gemm_ps_a_plan)
  *   recurrence (lstm*.hip)     AMS_LSTM_RING_X6, AMS_LSTM_RING_F16, AMS_LSTM_RING_BWD_F16 (arithmetic of the rings' recurrent products),
  *                              AMS_LSTM_RING_SAFE (write-through hand-off), AMS_LSTM_RING_CUS (pretend a smaller device: fallback tests)
  *   k-means                    AMS_KM_TRIES (0 = one workgroup per try), AMS_KM_SOFT (0 = soft accumulation inside kmeans_pass_kernel)
@@ -173,12 +174,19 @@ ams_status ams_gemm_ps(int M, int N, int K, const void* A_img, const void* B_img
 /* ams_gemm_ps_a_f32 (ABI 6): C[M,N] = A[M,K] . B[N,K]^T with A f32 (row pitch lda floats) and B a PS32 image -- the backward input-
  * gradient products dX = dU . W^T, W stored [Din, Dout] row-major, whose B image is ams_ps_pack_rows(W) (no transpose) and cut before
  * the step's product, while dU's bound only exists once the kernel that wrote it has run: A is cut inside the kernel (the 128-row side of
- * the tile).  K is split as ams_gemm_f32's fp16x3 form splits the same product on its 128 x 256 tile; the partial slabs go to ws
+ * the tile).  Tile width and k-split come from ams_gemm_ps_a_plan, the rule ams_gemm_f32's fp16x3 form follows for the same product; the partial slabs go to ws
  * (ams_gemm_ps_a_workspace_bytes(M, N, K); NULL / too small = fewer splits) and are added in split order -- the same terms, MFMA order,
  * accumulator sets, partition and reduce order, so the result is that of ams_gemm_f32 with the same bounds.  K >= 1, lda >= K,
  * lda, N, ldc multiples of 4; A, B_img, C, ws 16-byte aligned; M * lda * 4 and the image below 2 GB.  Replaces: the gradients of
  * utils/ops.py:366-383 (dynamic_rnn input projection: dX through [Wx_f | Wx_b]) and :501-503 (conv1d k = 1: dX). */
 size_t ams_gemm_ps_a_workspace_bytes(int M, int N, int K);
+/* ams_gemm_ps_a_plan (an addition, as ams_ps_pack_many: the ABI number stays): the tile width (256 or 320 columns), slab count and k per
+ * slab (a multiple of 32) that ams_gemm_ps_a_f32 takes for this shape with ws_bytes of slabs -- one rule, a cost model over the two
+ * tiles, which ams_gemm_f32's fp16x3 form follows for the same product (transB, uncapped, 128 x 256 configuration: its tile stays, its
+ * slab count is this one), so the two give the same bits.  ams_gemm_ps_a_workspace_bytes is splits * M * N * 4 of the plan with room for
+ * all its slabs.  Environment, read once: AMS_GEMM_DX_TILE=256 -> the 256 tile with its own slab rule for both forms (the plan before the
+ * 320 tile existed), =320 -> the 320 tile wherever its slabs fit. */
+ams_status ams_gemm_ps_a_plan(int M, int N, int K, size_t ws_bytes, int* tile_n, int* splits, int* kps);
 ams_status ams_gemm_ps_a_f32(int M, int N, int K, const float* A, long lda, const void* B_img, float* C, long ldc, const float* amax_a,
                              const float* amax_b, void* ws, size_t ws_bytes, void* stream);
 
