@@ -119,6 +119,10 @@ def _twin(a, b):
     C = a.shape[-1]
     if b.data_ptr() != a.data_ptr() + 4 * C or a.stride(-1) != 1 or b.stride(-1) != 1:
         return False
+    # ONE storage, not merely adjacent addresses: two separate allocations of a multiple of 512 bytes (biases of H = 96, 192, 288)
+    # often lie back to back in the caching allocator, and a view of 2C elements from `a` does not exist then
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
     return a.dim() == 1 or (a.stride(0) == 2 * C and b.stride(0) == 2 * C)
 
 

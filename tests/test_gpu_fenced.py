@@ -41,6 +41,7 @@ PS = 'test_gpu_gemm_ps'
 DX = 'test_gpu_gemm_ps_dx'
 BB = 'test_gpu_bss_batch'
 DP = 'test_gpu_dispatch_arms'
+RA = 'test_gpu_ring_arms'
 
 
 def _arm(cases, *head):
@@ -135,6 +136,11 @@ ROWS = [
     (DP, 'test_soft_kmeans_forward', _arm(arms.SOFT_FORWARD_CASES, 8, 4, 197)),
     (DP, 'test_l41_loss', (4, 4, True, True)), (DP, 'test_l41_loss', (16, 6, False, False)),
     (DP, 'test_dpcl_from_the_network_output', (60, 4, 2561)), (DP, 'test_dpcl_from_the_network_output', (45, 5, 77)),
+    # arms of the ring recurrence (tests/test_gpu_ring_arms.py), plain hand-off: 10 chains padded to 16 (six chains' worth of workgroups
+    # must leave without touching anything) in both arithmetics, a last workgroup of one unit, and the largest ring
+    (RA, 'test_ring_arm', (65, 5, 8, 61, '1', 'bf16x6_f32')), (RA, 'test_ring_arm', (65, 5, 8, 61, '1', 'fp16x3')),
+    (RA, 'test_ring_arm', (17, 6, 8, 97, '1', 'fp16x3')),
+    (RA, 'test_ring_arm', (17, 6, 8, 336, '1', 'bf16x6_f32')),
 ]
 
 # (module, test function, arguments, base, outcome)
@@ -156,6 +162,8 @@ ODD_ROWS = [
     (K1, 'test_optimizers', (), 4, 'passes'),
     (DP, 'test_hard_kmeans', _arm(arms.HARD_CASES, 20, 3, 8449, 3, True), 4, 'passes'),
     (DP, 'test_l41_loss', (4, 4, True, True), 4, 'passes'),
+    # rows of 4H = 244 floats stay 16-byte multiples, so x, the kernels and dout are all 4 bytes off as a slice of a flat buffer would be
+    (RA, 'test_ring_arm', (65, 5, 8, 61, '1', 'bf16x6_f32'), 4, 'passes'),
 ]
 
 
@@ -190,7 +198,7 @@ def host(t):
 # backward or of the five-tries kernels is therefore not seen by these rows (the hard and soft k-means FORWARD kernels read fenced
 # inputs in the test_gpu_kernels2.py rows).  test_gpu_many_speakers_kernels.py::test_soft_kmeans_backward calls
 # test_gpu_kmeans_soft.py's test and is 'not fenced' in the same way.
-UPLOADS = {E_: 'dev', K1: 'dev', K2: 'dev', DA: 'dev', PS: 'dev', DX: 'dev', MS: 'dev', DP: 'dev',
+UPLOADS = {E_: 'dev', K1: 'dev', K2: 'dev', DA: 'dev', PS: 'dev', DX: 'dev', MS: 'dev', DP: 'dev', RA: 'dev',
            DC: 'not fenced', KS: 'not fenced', KT: 'not fenced', BB: 'not fenced'}
 INPUTS_NOT_FENCED = [(DC, 'test_layer'), (KS, 'test_soft_kmeans_backward'), (KT, 'test_five_tries_per_read_is_bit_exact'),
                      (MS, 'test_soft_kmeans_backward'), (BB, 'test_edge_tiles'), (BB, 'test_potrf_depends_on_its_matrix_only')]
