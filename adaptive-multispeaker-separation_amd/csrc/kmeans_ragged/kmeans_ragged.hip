@@ -1,12 +1,10 @@
 // Hard k-means over segments of different numbers of points (include/ams_kmeans_ragged.h): libams_kmeans_ragged.so.
 //
-// The passes ARE the tuned hard passes of csrc/kmeans.hip, compiled a second time with AMS_KM_RAGGED: the same staging, distance
-// chains, lane trees and in-launch finish, so every running sum sees the same terms in the same order as in libams_hip.so -- only the
-// index arithmetic differs.  Where kmeans.hip computes (utterance, chunk, column) from blockIdx and takes L and G from its arguments, the
-// ragged build reads (segment, chunk, column) from the host-built work table and the segment's own length, chunk count and place among
-// the partial rows from p_off / g_off.  One launch per pass whatever the number of segments.
-#define AMS_KM_RAGGED 1
-#include "../kmeans.hip"
+// The passes ARE the tuned hard passes of libams_hip.so: the kernels of csrc/kmeans_hard.h instantiated with the geometry KmRagged where
+// csrc/kmeans.hip instantiates them with KmDense, so every running sum sees the same terms in the same order; only the index arithmetic,
+// which the geometry states, differs: (segment, chunk, column) from the host-built work table, the segment's length, chunk count and
+// place among the partial rows from p_off / g_off.  One launch per pass whatever the number of segments; only KmRagged::pair's (E, C).
+#include "../kmeans_hard.h"
 #include "../../../include/ams_kmeans_ragged.h"
 
 thread_local int g_ams_last_hip_error = 0;      // (common.h: this library keeps its own)
@@ -24,23 +22,22 @@ __global__ void kmr_init_kernel(const float* __restrict__ xn, const long* __rest
     cent[i] = xn[(p_off[r / tries] + idx[rc]) * E + e];
 }
 
-bool kmr_pair(int E, int C) { return (E == 40 || E == 8) && C >= 2 && C <= 6; }
 bool kmr_sizes(int R, int tries, long Gtot) { return R >= 1 && tries >= 1 && Gtot >= R && 4 * Gtot * (long)tries < (1L << 31); }
 
 // five tries per read of the points: E = 40, C = 2, tries a multiple of 5, 32-bit buffer offsets inside every segment
 bool kmr_tries_kernel(int tries, long Pmax, int E, int C) { return E == 40 && C == 2 && tries % TQ == 0 && Pmax * E * 4 < (1L << 31); }
 
-KmArgs kmr_args(const float* xn, const float* w, const int32_t* tab, const long* p_off, const long* g_off, const float* cent, int R,
+KmRagged::Args kmr_args(const float* xn, const float* w, const int32_t* tab, const long* p_off, const long* g_off, const float* cent, int R,
                 int tries, long Gtot) {
-    KmArgs a{};
+    KmRagged::Args a{};
     a.xn = xn; a.w = w; a.cent = cent; a.b = R; a.tries = tries; a.beta = -1.0f; a.one = 1.0f;
     a.tab = tab; a.p_off = p_off; a.g_off = g_off; a.Gtot = (int)Gtot;
     return a;
 }
 
-KtArgs kmr_targs(const float* xn, const float* w, const int32_t* tab, const long* p_off, const long* g_off, const float* cent, int R,
+KmRagged::TArgs kmr_targs(const float* xn, const float* w, const int32_t* tab, const long* p_off, const long* g_off, const float* cent, int R,
                  int tries) {
-    KtArgs k{};
+    KmRagged::TArgs k{};
     k.xn = xn; k.w = w; k.cent = cent; k.b = R; k.tries = tries;
     k.tab = tab; k.p_off = p_off; k.g_off = g_off;
     return k;
@@ -82,13 +79,13 @@ ams_status ams_kmr_tables(const int64_t* p_off, int R, int64_t* g_off, int32_t* 
 }
 
 size_t ams_kmr_workspace_bytes(int R, int tries, long Gtot, int E, int C) {
-    if (!kmr_pair(E, C) || !kmr_sizes(R, tries, Gtot)) return 0;
+    if (!KmRagged::pair(E, C) || !kmr_sizes(R, tries, Gtot)) return 0;
     return sizeof(float) * (size_t)tries * 4 * (size_t)Gtot * C * (E + 1);
 }
 
 ams_status ams_kmr_init(const float* xn, const int64_t* p_off, const int32_t* init_idx, float* centroids, int R, int tries, int E, int C,
                         void* stream) {
-    AMS_REQUIRE(xn && p_off && init_idx && centroids && R >= 1 && tries >= 1 && kmr_pair(E, C));
+    AMS_REQUIRE(xn && p_off && init_idx && centroids && R >= 1 && tries >= 1 && KmRagged::pair(E, C));
     const long n = (long)R * tries * C * E;
     AMS_REQUIRE(n < (1L << 31) * 256);
     hipLaunchKernelGGL(kmr_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, xn, (const long*)p_off,
@@ -99,64 +96,56 @@ ams_status ams_kmr_init(const float* xn, const int64_t* p_off, const int32_t* in
 ams_status ams_kmr_iterate(const float* xn, const float* w, const int32_t* tab, const int64_t* p_off, const int64_t* g_off,
                            const float* cent_in, float* cent_out, int R, int tries, long Gtot, long Pmax, int E, int C, void* ws,
                            size_t ws_bytes, void* tickets, void* stream) {
-    AMS_REQUIRE(xn && tab && p_off && g_off && cent_in && cent_out && ws && tickets && kmr_pair(E, C) && kmr_sizes(R, tries, Gtot) &&
+    AMS_REQUIRE(xn && tab && p_off && g_off && cent_in && cent_out && ws && tickets && KmRagged::pair(E, C) && kmr_sizes(R, tries, Gtot) &&
                 Pmax >= 1);
     if (ws_bytes < ams_kmr_workspace_bytes(R, tries, Gtot, E, C)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     if (kmr_tries_kernel(tries, Pmax, E, C)) {
-        KtArgs k = kmr_targs(xn, w, tab, (const long*)p_off, (const long*)g_off, cent_in, R, tries);
+        KmRagged::TArgs k = kmr_targs(xn, w, tab, (const long*)p_off, (const long*)g_off, cent_in, R, tries);
         k.part = (float*)ws; k.tickets = (unsigned*)tickets; k.fin_out = cent_out;
         const dim3 grid((unsigned)(4 * Gtot * (tries / TQ)));       // (try group, unit of the table)
-        if (w) hipLaunchKernelGGL(kmeans_hard_tries_kernel<true>, grid, dim3(640), KT_LDS_BYTES, st, k);
-        else hipLaunchKernelGGL(kmeans_hard_tries_kernel<false>, grid, dim3(640), KT_LDS_BYTES, st, k);
+        if (w) hipLaunchKernelGGL((kmeans_hard_tries_kernel<KmRagged, true>), grid, dim3(640), KT_LDS_BYTES, st, k);
+        else hipLaunchKernelGGL((kmeans_hard_tries_kernel<KmRagged, false>), grid, dim3(640), KT_LDS_BYTES, st, k);
         return ams_check_launch();
     }
-    KmArgs a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent_in, R, tries, Gtot);
+    KmRagged::Args a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent_in, R, tries, Gtot);
     a.part = (float*)ws; a.tickets = (unsigned*)tickets; a.fin_out = cent_out;
-    if (C > 4) {
-        // five and six clusters: three sweeps of the chunk, two clusters' sums at a time (kmeans_hard_acc_grouped_kernel)
-        const dim3 grid((unsigned)(Gtot * tries));
-#define AMS_KMG(EE, CC) do { if (w) hipLaunchKernelGGL((kmeans_hard_acc_grouped_kernel<EE, CC, true>), grid, dim3(256), 0, st, a); \
-                             else hipLaunchKernelGGL((kmeans_hard_acc_grouped_kernel<EE, CC, false>), grid, dim3(256), 0, st, a); } while (0)
-        if (E == 40 && C == 5) AMS_KMG(40, 5); else if (E == 40) AMS_KMG(40, 6); else if (C == 5) AMS_KMG(8, 5); else AMS_KMG(8, 6);
-#undef AMS_KMG
-        return ams_check_launch();
-    }
-    return launch_pass<HARD_ACC>(a, R * tries, E, C, st);
+    if (C > 4) return launch_grouped<KmRagged>(a, E, C, st);
+    return launch_pass<KmRagged, HARD_ACC>(a, R * tries, E, C, st);
 }
 
 ams_status ams_kmr_inertia(const float* xn, const float* w, const int32_t* tab, const int64_t* p_off, const int64_t* g_off,
                            const float* cent, float* inertia, int R, int tries, long Gtot, long Pmax, int E, int C, void* ws,
                            size_t ws_bytes, void* tickets, void* stream) {
-    AMS_REQUIRE(xn && tab && p_off && g_off && cent && inertia && ws && tickets && kmr_pair(E, C) && kmr_sizes(R, tries, Gtot) && Pmax >= 1);
+    AMS_REQUIRE(xn && tab && p_off && g_off && cent && inertia && ws && tickets && KmRagged::pair(E, C) && kmr_sizes(R, tries, Gtot) && Pmax >= 1);
     if (ws_bytes < ams_kmr_workspace_bytes(R, tries, Gtot, E, C)) return AMS_E_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     if (kmr_tries_kernel(tries, Pmax, E, C)) {
-        KtArgs k = kmr_targs(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, tries);
+        KmRagged::TArgs k = kmr_targs(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, tries);
         k.part = (float*)ws; k.tickets = (unsigned*)tickets; k.fin_out = inertia;
         const dim3 grid((unsigned)(2 * Gtot * (tries / TQ)));       // (try group, column pair of the table)
-        if (w) hipLaunchKernelGGL(kmeans_hard_tries_final_kernel<true>, grid, dim3(640), 2 * 128 * 40 * sizeof(float), st, k);
-        else hipLaunchKernelGGL(kmeans_hard_tries_final_kernel<false>, grid, dim3(640), 2 * 128 * 40 * sizeof(float), st, k);
+        if (w) hipLaunchKernelGGL((kmeans_hard_tries_final_kernel<KmRagged, true>), grid, dim3(640), 2 * 128 * 40 * sizeof(float), st, k);
+        else hipLaunchKernelGGL((kmeans_hard_tries_final_kernel<KmRagged, false>), grid, dim3(640), 2 * 128 * 40 * sizeof(float), st, k);
         return ams_check_launch();
     }
-    KmArgs a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, tries, Gtot);
+    KmRagged::Args a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, tries, Gtot);
     a.part = (float*)ws; a.tickets = (unsigned*)tickets; a.fin_out = inertia;
-    return launch_pass<HARD_FINAL>(a, R * tries, E, C, st);
+    return launch_pass<KmRagged, HARD_FINAL>(a, R * tries, E, C, st);
 }
 
 ams_status ams_kmr_select(const float* inertia, const float* centroids, int32_t* best, float* selected, int R, int tries, int E, int C,
                           void* stream) {
-    AMS_REQUIRE(inertia && centroids && best && selected && R >= 1 && tries >= 1 && kmr_pair(E, C));
+    AMS_REQUIRE(inertia && centroids && best && selected && R >= 1 && tries >= 1 && KmRagged::pair(E, C));
     hipLaunchKernelGGL(kmeans_select_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, inertia, centroids, best, selected, R, tries, C * E);
     return ams_check_launch();
 }
 
 ams_status ams_kmr_labels(const float* xn, const float* w, const int32_t* tab, const int64_t* p_off, const int64_t* g_off,
                           const float* cent, int32_t* labels, int R, long Gtot, int E, int C, void* stream) {
-    AMS_REQUIRE(xn && tab && p_off && g_off && cent && labels && kmr_pair(E, C) && kmr_sizes(R, 1, Gtot));
-    KmArgs a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, 1, Gtot);
+    AMS_REQUIRE(xn && tab && p_off && g_off && cent && labels && KmRagged::pair(E, C) && kmr_sizes(R, 1, Gtot));
+    KmRagged::Args a = kmr_args(xn, w, tab, (const long*)p_off, (const long*)g_off, cent, R, 1, Gtot);
     a.labels = labels;                                              // (no partial sums, no tickets: HARD_LABELS stores labels only)
-    return launch_pass<HARD_LABELS>(a, R, E, C, (hipStream_t)stream);
+    return launch_pass<KmRagged, HARD_LABELS>(a, R, E, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

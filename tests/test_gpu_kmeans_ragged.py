@@ -158,6 +158,25 @@ def test_other_arms(E, C, tries, kind):
     _check([900, 8192 + 257], E, C, tries, False, [kind, kind], against_run=False)
 
 
+def _every_pair():
+    from ams_hip import kmeans_ragged as kr
+    return sorted(kr.PAIRS)
+
+
+@pytest.mark.parametrize('end', [True, False])
+@pytest.mark.parametrize('kind', [None, 'mask'])
+@pytest.mark.parametrize('order', ['forward', 'reversed'])
+@pytest.mark.parametrize('E,C', _every_pair())
+def test_the_per_try_pass_of_every_pair(E, C, order, kind, end):
+    """tries = 2: every (E, C) the library takes, (40, 2) included, runs the per-try pass -- accumulation (the grouped kernel at C = 5, 6),
+    inertia and labels -- over a full chunk plus 257 points (a second chunk whose second slab has one lane), a segment shorter than a
+    wave, and an exact chunk, so that the segment after it starts on a chunk edge."""
+    sizes = [8449, 37, 8192]
+    if order == 'reversed':
+        sizes = sizes[::-1]
+    assert _check(sizes, E, C, 2, end, [kind] * 3) == ITERS + 4
+
+
 def test_empty_cluster_gives_the_oracles_nan():
     """Two seed indices that hold the SAME point: every point is as near to centroid 0 as to centroid 1, the tie goes to 0, cluster 1 is
     empty and its centroid is 0 / 0 after the first update.  The assignments against the NaN centroid that follow go as the oracle's
@@ -183,7 +202,8 @@ def test_empty_cluster_gives_the_oracles_nan():
             assert np.array_equal(lab[rows].cpu().numpy(), ref[1][0]) and int(best[r]) == ref[2][0], (iters, r)
 
 
-@pytest.mark.parametrize('E,C,tries,kinds', [(40, 2, 5, None), (40, 2, 10, ['mask', 'real', 'zero']), (8, 3, 2, None), (40, 6, 5, None)])
+@pytest.mark.parametrize('E,C,tries,kinds', [(40, 2, 5, None), (40, 2, 10, ['mask', 'real', 'zero']), (8, 3, 2, None), (40, 6, 5, None),
+                                             (40, 4, 2, None), (8, 5, 2, None)])
 @pytest.mark.parametrize('base', [0, 4, 12])
 def test_inside_fenced_buffers(E, C, tries, kinds, base):
     """Red zones around every operand, NaN-filled outputs and workspaces, the points and weights at an odd base: nothing outside the

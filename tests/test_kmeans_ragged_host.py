@@ -40,7 +40,7 @@ def test_header_and_exports():
 
 
 def test_libams_hip_keeps_its_exports():
-    """libams_hip.so exports exactly what include/ams.h declares (version 10), as before the ragged build of csrc/kmeans.hip existed, and
+    """libams_hip.so exports exactly what include/ams.h declares (version 10), as before the ragged geometry of csrc/kmeans_hard.h existed, and
     none of the other libraries gained a ragged symbol."""
     from ams_hip import _lib, stitch, stitch_batch
     want = set(_lib.parse_header(_lib.HEADER_PATH))
