@@ -615,6 +615,29 @@ class Network(object):
             est[b0:b0 + n] = out[:n]
         return est
 
+    # ---- live streams: the same chunks, borders and cross-fade, one chunk behind samples that arrive block by block
+    def open_streams(self, n, hop=None, batch_size=None):
+        """-> ams_hip.stream.StreamSeparator for n parallel streams of mono float32 samples at config.fs: push(blocks) takes a block of any
+        size per stream and returns what has become final, one chunk (chunk_size samples) behind; close(s) returns the rest.  The ready
+        chunks of ALL streams of a push go through infer_chunks together, in passes of batch_size rows (default: the model's batch size),
+        and are tracked and cross-faded by kernels whose launch count does not depend on n (include/ams_stream.h).  Only the default
+        clustering='chunk' of separate_recording can run this way: it is causal in chunk order.
+
+        A chunk's k-means seeds depend on the pass and the row of the batch it lands in (as in separate_recordings), and
+        here that is decided by how the blocks arrive: a stream's output is DEFINED as ams_hip.stitch.stitch of the estimates its chunks
+        got, bit for bit.  It equals separate_recording of the same samples only where those estimates are equal."""
+        from ams_hip import stitch as St
+        from ams_hip import stream as Sm
+        self._refuse_unless_separating()
+        L = int(self.args['chunk_size'])
+        H = St.default_hop(L) if hop is None else int(hop)
+        St.check_geometry(L, H)
+        if int(n) < 1:
+            raise ValueError('open_streams: at least one stream, got %d' % n)
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError('open_streams: a batch size of at least 1, got %d' % batch_size)
+        return Sm.StreamSeparator(lambda mix: self.infer_chunks(mix, batch_size), int(n), self.S, L, H, device=get_default_graph().device)
+
     # ---- recording-level clustering (DESIGN.md 4.10): the embeddings of ALL chunks of a recording are one point set for one k-means,
     # so every chunk shares its centroids and the labels mean the same speaker everywhere: no border permutation is left to decide
     CLUSTER_CAP_BYTES = 8 << 30                # packed points (Ctot TF E 4 bytes) clustered at a time, unless the caller says otherwise
