@@ -24,7 +24,22 @@
 #ifndef AMS_DPCL_DBG
 #define AMS_DPCL_DBG 0
 #endif
+// the streamed backward (dpcl_bwd_u2_kernel<E, S, D>): groups in flight per wave, resident workgroups per CU it is built for
+#ifndef AMS_DPCL_STREAM_DEPTH
+#define AMS_DPCL_STREAM_DEPTH 2
+#endif
+#ifndef AMS_DPCL_STREAM_LINEAR
+#define AMS_DPCL_STREAM_LINEAR 1
+#endif
+#ifndef AMS_DPCL_STREAM_STORE_LINEAR
+#define AMS_DPCL_STREAM_STORE_LINEAR 1
+#endif
+#ifndef AMS_DPCL_STREAM_WGS
+#define AMS_DPCL_STREAM_WGS 4
+#endif
 namespace {
+
+typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int CHUNK = 2048;            // points per workgroup in the Gram pass
 
@@ -992,8 +1007,38 @@ __global__ __launch_bounds__(256, 2) void dpcl_bwd_u_kernel(const float* __restr
 // per 64, and that VALU work outweighs the barriers it removes.  It keeps the staged form.)
 constexpr int BCH2 = 1024;             // points per 256-thread workgroup, backward (16 groups of 16 points per wave)
 
-template <int EC, int SC>
-__global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restrict__ U, const float* __restrict__ Y,
+// Round 14: the same kernel fed from a wave-private LDS ring (template argument D > 0 = ring depth in groups; D = 0 is the register
+// rotation above, kept for unaligned bases and as the A/B arm, AMS_DPCL_STREAM=0).  A group's loads -- its 16 rows of U, the labels,
+// 1/|u| -- are five `buffer_load ... lds` instructions (LDS-DMA: no destination registers) into one of the wave's D slots.  The rows
+// come as they lie in memory, 2560 contiguous bytes in two and a half 1-KiB pieces (lane x 16 bytes each), and a lane takes its three
+// float4 with `ds_read_b128` at row e_lo, pieces slot, 4 + slot, min(8 + slot, 9): the values the register loads returned, and the
+// arithmetic from there on is the same text (dU and max |dU| have the register arm's bits).  dU leaves the same way round: the lanes
+// put the group's rows together in 2560 bytes of LDS and the wave stores them as contiguous pieces.  Measured alone at 64 x 20480
+// (profiles/r14_a_dpcl_stream_standalone.txt): the ring with the register arm's per-lane addresses (-DAMS_DPCL_STREAM_LINEAR=0
+// -DAMS_DPCL_STREAM_STORE_LINEAR=0) 107 against 110 us -- bytes in flight were not what held the kernel --, contiguous loads 104,
+// contiguous loads and stores 96.  A wave reads only what it fetched itself: no barrier, completion is a counted s_waitcnt.  Rows past
+// the utterance's end are cut by the buffer descriptors (num_records = the utterance's bytes: zeros, nothing is clamped); label slots
+// >= S, the 1/|u| lanes of slots 1 .. 3 and the upper half of the third piece carry an offset beyond any descriptor.
+//   slot image (STREAM_SLOT bytes): rows [16][160 B] in 3 KiB | Y [s][e_lo] (256 B) | 1/|u| [e_lo] (64 of 256 B)
+// Geometry at 64 x 20480: STREAM_BCH = 1280 points per workgroup = 20 groups per wave, 16 x 64 = 1024 workgroups = one round of the
+// 256 CUs at four workgroups each (112-124 registers, 38 KiB of LDS per workgroup).
+constexpr int STREAM_BCH = 1280;       // points per 256-thread workgroup of the streamed backward
+constexpr int STREAM_DEPTH = AMS_DPCL_STREAM_DEPTH;      // groups in flight per wave
+constexpr int STREAM_WG_PER_CU = AMS_DPCL_STREAM_WGS;    // resident workgroups per CU the kernel is built for (registers and LDS)
+constexpr int STREAM_SLOT = 3 * 1024 + 256 + 256;
+constexpr bool STREAM_STORE_LINEAR = AMS_DPCL_STREAM_STORE_LINEAR != 0;        // dU leaves through LDS as contiguous pieces
+constexpr int STREAM_OUT = 16 * 40 * 4;                         // a group's dU rows
+constexpr bool STREAM_LINEAR = AMS_DPCL_STREAM_LINEAR != 0;     // the U pieces of a slot hold the group's rows as they lie in memory
+static_assert(STREAM_DEPTH >= 1 && STREAM_DEPTH <= 4 && STREAM_BCH % 64 == 0 && STREAM_WG_PER_CU * 4 * (STREAM_DEPTH * STREAM_SLOT + STREAM_OUT) <= 160 * 1024,
+              "the rings of a CU's resident workgroups fit its 160 KiB of LDS");
+constexpr int STREAM_DMAS = 5;         // LDS-DMA instructions per group
+constexpr int STREAM_STORES = 3;       // dU store instructions of a FULL group (16 live rows: every piece has a live lane).  Only the last group of an
+                                       // utterance can be shorter and skip one; the steady-state wait below never counts that group's stores
+
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+
+template <int EC, int SC, int D = 0>
+__global__ __launch_bounds__(256, (D > 0 ? STREAM_WG_PER_CU : 1)) void dpcl_bwd_u2_kernel(const float* __restrict__ U, const float* __restrict__ Y,
                                                           const float* __restrict__ cntp, const float* __restrict__ mats,
                                                           const float* __restrict__ inv, const float* __restrict__ upstream,
                                                           float* __restrict__ dU, long TF, unsigned* __restrict__ amax_out) {
@@ -1067,12 +1112,13 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
         }
     }
 #endif
-    const long p_begin = (long)c * BCH2, p_end = min(TF, p_begin + BCH2);
+    constexpr int BCH = D > 0 ? STREAM_BCH : BCH2;
+    const long p_begin = (long)c * BCH, p_end = min(TF, p_begin + BCH);
     const float* Ub = U + (long)b * TF * E;
     const float* Yb = Y + (long)b * TF * S;
     const float* ib = inv + (long)b * TF;
     float* dUb = dU + (long)b * TF * E;
-    constexpr int NG = BCH2 / 16 / 4;               // groups per wave
+    constexpr int NG = BCH / 16 / 4;                // groups per wave
     // which of the lane's three float4 are embedding values, which one is the label vector
     const bool uval[NJ] = {true, true, 32 + 4 * slot < E};
     const bool ylane = (32 + 4 * slot == E);
@@ -1088,6 +1134,7 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
         for (int s = 0; s < 4; ++s) g.y[s] = (s < S) ? Yb[pc * S + s] : 0.f;
         g.iv = ib[pc];
     };
+    unsigned char* wout = nullptr;                  // (streamed arm) the wave's 2560 bytes of LDS for a group's dU rows
     auto compute = [&](long g0, const Grp& g) {
         const long p = g0 + e_lo;
         const bool live = p < p_end;
@@ -1179,16 +1226,115 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
                 o.y = active ? (dd[ft][1] - z[ft][1] * dot) * iv : dd[ft][1] * iv;
                 o.z = active ? (dd[ft][2] - z[ft][2] * dot) * iv : dd[ft][2] * iv;
                 o.w = active ? (dd[ft][3] - z[ft][3] * dot) * iv : dd[ft][3] * iv;
-                reinterpret_cast<float4*>(dUb + p * E)[4 * ft + slot] = o;
+                if constexpr (D > 0 && STREAM_STORE_LINEAR) *reinterpret_cast<float4*>(wout + e_lo * (E * 4) + (4 * ft + slot) * 16) = o;
+                else reinterpret_cast<float4*>(dUb + p * E)[4 * ft + slot] = o;
                 amax_f = fmaxf(fmaxf(amax_f, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
             }
+        }
+        if constexpr (D > 0 && STREAM_STORE_LINEAR) {
+            // the streamed arm's way out: the live rows of the group were put together in the wave's own 2560 bytes of LDS, at the positions
+            // they have in memory, and leave as whole 1-KiB pieces -- two and a half contiguous stores instead of three of sixteen 64-byte
+            // runs.  LDS operations of one wave execute in order: no barrier between its writes and its reads
+            __builtin_amdgcn_wave_barrier();
+            const int nbytes = (int)min(16L, p_end - g0) * (E * 4);             // the group's live rows (wave-uniform)
+            unsigned char* const dst = reinterpret_cast<unsigned char*>(dUb + g0 * E);
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int off = i * 1024 + lane * 16;
+                if (off < nbytes && !(AMS_DPCL_DBG & 8)) *reinterpret_cast<float4*>(dst + off) = *reinterpret_cast<const float4*>(wout + off);
+            }
+            __builtin_amdgcn_wave_barrier();
         }
     };
     // three register buffers in rotation: while group n is in the MFMAs, groups n + 1 and n + 2 are in flight (one wave keeps
     // 5 KB outstanding, a CU's 16 waves 80 KB -- what 6 TB/s x 3 us of loaded latency asks of each of the 256 CUs)
-    Grp g0b, g1b, g2b;
     const long w0 = p_begin + (long)wave * (NG * 16);
     const long w_end = min(p_end, w0 + (long)NG * 16);
+    if constexpr (D > 0) {
+        __shared__ __attribute__((aligned(1024))) unsigned char ring[4 * D * STREAM_SLOT];
+        __shared__ __attribute__((aligned(16))) unsigned char outb[STREAM_STORE_LINEAR ? 4 * STREAM_OUT : 16];
+        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+        wout = outb + (STREAM_STORE_LINEAR ? wave_u * STREAM_OUT : 0);
+        unsigned char* const wring = ring + wave_u * (D * STREAM_SLOT);
+        const unsigned lds_w = (unsigned)(uintptr_t)(lds_void*)ring + (unsigned)(wave_u * (D * STREAM_SLOT));
+        // raw buffer descriptors {base lo, base hi (stride 0), num_records in bytes, flags} of the utterance's three arrays (gemm_ps.hip)
+        auto rsrc = [](const void* p, long bytes) {
+            const unsigned long long a = (unsigned long long)(uintptr_t)p;
+            i32x4_t r = {(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
+            r.x = __builtin_amdgcn_readfirstlane(r.x); r.y = __builtin_amdgcn_readfirstlane(r.y);
+            r.z = __builtin_amdgcn_readfirstlane(r.z); r.w = __builtin_amdgcn_readfirstlane(r.w);
+            return r;
+        };
+        const i32x4_t rsU = rsrc(Ub, TF * E * 4), rsY = rsrc(Yb, TF * S * 4), rsI = rsrc(ib, TF * 4);       // (host: TF * E * 4 < 2^31)
+        constexpr unsigned OOR = 0x80000000u;       // beyond every descriptor: the lane's piece is zeros and no memory is touched
+        const unsigned q2 = (unsigned)min(8 + slot, E / 4 - 1) * 16u;
+        // the wave's range again from the wave-uniform wave number, so that the loop below and its waits are scalar branches
+        const int u0 = (int)p_begin + wave_u * (NG * 16);           // first point, inside the utterance
+        const int ngrp = __builtin_amdgcn_readfirstlane(((int)min(p_end, (long)u0 + NG * 16) - u0 + 15) >> 4);     // groups (<= 0: nothing to do)
+        // The five loads of group n into slot n % D, ONE asm statement: hipcc, which would order every LDS read behind an LDS-DMA it knows
+        // of with vmcnt(0), does not see them.  The lgkmcnt(0) in front keeps the DMA behind the wave's own reads of the slot it refills.
+        auto issue = [&](int n) {
+            const unsigned p = (unsigned)(u0 + 16 * n + e_lo);      // point inside the utterance (< TF + 16)
+            const unsigned vu = p * (unsigned)(E * 4);
+            unsigned v0, v1, v2;
+            if (STREAM_LINEAR) {                    // the group's 16 rows = 2560 contiguous bytes: two whole 1-KiB pieces and half a third
+                v0 = (unsigned)(u0 + 16 * n) * (unsigned)(E * 4) + (unsigned)lane * 16u; v1 = v0 + 1024u;
+                v2 = lane < (16 * E * 4 - 2048) / 16 ? v0 + 2048u : OOR;
+            } else { v0 = vu + (unsigned)slot * 16u; v1 = v0 + 64u; v2 = vu + q2; }
+            const unsigned vy = slot < S ? (p * (unsigned)S + (unsigned)slot) * 4u : OOR;
+            const unsigned vi = slot == 0 ? p * 4u : OOR;
+            const unsigned l0 = lds_w + (unsigned)((n % D) * STREAM_SLOT), l1 = l0 + 1024u, l2 = l0 + 2048u, l3 = l0 + 3072u, l4 = l0 + 3328u;
+            unsigned keep;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\t"
+                         "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %11, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %7, %11, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %8, %11, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dword %9, %12, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dword %10, %13, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep) : "s"(l0), "s"(l1), "s"(l2), "s"(l3), "s"(l4), "v"(v0), "v"(v1), "v"(v2), "v"(vy), "v"(vi),
+                           "s"(rsU), "s"(rsY), "s"(rsI) : "memory");
+        };
+        auto take = [&](int n, Grp& g) {
+            const unsigned char* const sl = wring + (n % D) * STREAM_SLOT;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                g.q[j] = *reinterpret_cast<const float4*>(STREAM_LINEAR ? sl + e_lo * (E * 4) + (j < 2 ? (unsigned)(4 * j + slot) * 16u : q2)
+                                                                        : sl + j * 1024 + lane * 16);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) g.y[s] = (s < S) ? *reinterpret_cast<const float*>(sl + 3072 + (s * 16 + e_lo) * 4) : 0.f;
+            g.iv = *reinterpret_cast<const float*>(sl + 3328 + e_lo * 4);
+        };
+        // A wave's VMEM operations go out in this order (cntp, mats and upstream were read, by loads hipcc counts, before the first DMA;
+        // a wait of hipcc's for them that lands behind a DMA only waits for more than it needs, the counter retires in order):
+        //   DMA(0) .. DMA(D - 1) | then per group n:  wait(n), take(n), DMA(n + D) if it exists, the 3 stores of compute(n)
+        // DMA(n) went out in front of compute(max(n - D, 0)) -- so at wait(n) the operations YOUNGER than DMA(n) are
+        //   the DMAs of groups n + 1 .. min(n + D - 1, ngrp - 1)                        5 each
+        //   the stores of compute(max(n - D, 0)) .. compute(n - 1)                       3 each
+        // and vmcnt(that number) says DMA(n) has landed.  In the steady state (n >= D and group n + D - 1 exists) that is
+        // 5 (D - 1) + 3 D -- the counted stores belong to groups that have at least D - 1 groups behind them, so they are full groups
+        // and issue all three; at a wave's first D and last D - 1 groups the wait counts the DMAs only (a smaller number: it waits for
+        // more than it needs, never for less).  The counter retires loads and stores in the order of issue (gfx9: one vmcnt for both,
+        // which hipcc's own waits rely on as well).  No other VMEM operation is issued inside the loop.
+        if (ngrp > 0) {
+#pragma unroll
+            for (int n = 0; n < D; ++n) if (n < ngrp) issue(n);
+            Grp g;
+#pragma unroll 1
+            for (int n = 0; n < ngrp; ++n) {
+                const int rem = min(D - 1, ngrp - 1 - n);
+                if (n >= D && rem == D - 1) wait_vmcnt<STREAM_DMAS * (D - 1) + STREAM_STORES * D>();
+                else if (D > 3 && rem == 3) wait_vmcnt<STREAM_DMAS * 3>();
+                else if (D > 2 && rem == 2) wait_vmcnt<STREAM_DMAS * 2>();
+                else if (D > 1 && rem == 1) wait_vmcnt<STREAM_DMAS>();
+                else wait_vmcnt<0>();
+                take(n, g);
+                if (n + D < ngrp) issue(n + D);
+                compute((long)u0 + 16 * n, g);
+            }
+        }
+    } else {
+    Grp g0b, g1b, g2b;
     if (w0 < w_end) fetch(w0 + e_lo, g0b);
     if (w0 + 16 < w_end) fetch(w0 + 16 + e_lo, g1b);
 #pragma unroll 1
@@ -1202,6 +1348,7 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
         if (g + 64 < w_end) fetch(g + 64 + e_lo, g1b);
         compute(g + 32, g2b);
     }
+    }
     if (amax_out && AMS_DPCL_AMAX) {                // max |dU|: the operand bound of the products that read dU
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) amax_f = fmaxf(amax_f, __shfl_xor(amax_f, o));
@@ -1214,9 +1361,22 @@ __global__ __launch_bounds__(256) void dpcl_bwd_u2_kernel(const float* __restric
     }
 }
 
+// AMS_DPCL_STREAM=0: the register-fed backward everywhere (the A/B arm); read once
+bool dpcl_stream_on() {
+    static const bool v = [] { const char* e = getenv("AMS_DPCL_STREAM"); return !(e && e[0] == '0'); }();
+    return v;
+}
+
 }  // namespace
 
 extern "C" {
+
+// geometry of the streamed backward, for tests and tools: out[0] = points per workgroup, out[1] = ring depth in groups, out[2] = resident
+// workgroups per CU, out[3] = points per group, out[4] = waves per workgroup; returns 1 when the streamed form is switched on
+int ams_dpcl_stream_geometry(int* out) {
+    if (out) { out[0] = STREAM_BCH; out[1] = STREAM_DEPTH; out[2] = STREAM_WG_PER_CU; out[3] = 16; out[4] = 4; }
+    return dpcl_stream_on() ? 1 : 0;
+}
 
 size_t ams_dpcl_workspace_bytes(int B, long TF, int E, int S) {
     const int NT = ceil_div(E + S, 16), Z = NT * 16;
@@ -1357,6 +1517,14 @@ ams_status ams_dpcl_loss_bwd_u(const float* U, const float* Y, const float* inv,
         case 2: hipLaunchKernelGGL((dpcl_bwd_u_kernel<2>), grid, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, E, S, amax_out); break;
         case 3: {
             const bool al = (((uintptr_t)U & 15) == 0) && (((uintptr_t)dU & 15) == 0);
+            // the streamed form: aligned bases, an utterance below 2^31 bytes (32-bit buffer offsets), AMS_DPCL_STREAM != 0
+            const bool stream = al && dpcl_stream_on() && (E == 40) && (S == 2 || S == 3) && TF * E * 4 < (1L << 31) - 16 * E * 4;
+            if (stream) {
+                const dim3 grids(ceil_div(TF, STREAM_BCH), B);
+                if (S == 2) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 2, STREAM_DEPTH>), grids, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
+                else hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 3, STREAM_DEPTH>), grids, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
+                break;
+            }
             const dim3 grid2(ceil_div(TF, BCH2), B);
             if (E == 40 && S == 2 && al) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 2>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);
             else if (E == 40 && S == 3 && al) hipLaunchKernelGGL((dpcl_bwd_u2_kernel<40, 3>), grid2, dim3(256), 0, st, U, Y, cntp, mats, inv, upstream, dU, TF, amax_out);

@@ -27,6 +27,8 @@
  *   recurrence (lstm*.hip)     AMS_LSTM_RING_X6, AMS_LSTM_RING_F16, AMS_LSTM_RING_BWD_F16 (arithmetic of the rings' recurrent products),
  *                              AMS_LSTM_RING_SAFE (write-through hand-off), AMS_LSTM_RING_CUS (pretend a smaller device: fallback tests)
  *   k-means                    AMS_KM_TRIES (0 = one workgroup per try), AMS_KM_SOFT (0 = soft accumulation inside kmeans_pass_kernel)
+ *   fused loss (csrc/dpcl.hip) AMS_DPCL_STREAM (0 = ams_dpcl_loss_bwd_u feeds its E = 40 kernel from registers, not from the LDS-DMA ring:
+ *                              the same bits)
  */
 #ifndef AMS_H
 #define AMS_H
@@ -377,6 +379,10 @@ ams_status ams_dpcl_loss_fwd_u(const float* U, const float* Y, float* inv, float
                                int counts_ready, void* ws, size_t ws_bytes, void* stream);
 ams_status ams_dpcl_loss_bwd_u(const float* U, const float* Y, const float* inv, const float* upstream, float* dU, int B, long TF,
                                int E, int S, const void* ws, void* stream);
+/* Work geometry of the streamed E = 40 backward, for tests and tools (no part of the calling convention): out[0] = points per
+   workgroup, out[1] = groups a wave keeps in flight (ring depth), out[2] = resident workgroups per CU the kernel is built for,
+   out[3] = points per group, out[4] = waves per workgroup.  Returns 1 when the streamed form is in use, 0 under AMS_DPCL_STREAM=0. */
+int ams_dpcl_stream_geometry(int* out);
 
 /* ---- enhance-layer output stage   models/network.py:640-660 ----
  * u [B,S,TF] = Conv1D output of the enhance stack (rows (b,s)); X [B,TF] mixture representation.
