@@ -1,131 +1,27 @@
 // Whole recordings (include/ams_stitch.h): chunk gather, border table, border permutations and tracks, cross-fade.
 // A library of its own (libams_stitch.so): include/ams.h and libams_hip.so are untouched.  Built with -ffp-contract=off: the cross-fade
 // is two rounded products and one rounded add, and the border table has one summation order per alignment arm.  All four are
-// bandwidth-bound streaming / reduction kernels: no MFMA, no atomics, no scratch.
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
+// bandwidth-bound streaming / reduction kernels: no MFMA, no atomics, no scratch.  The arithmetic is stitch_core.h's, which
+// libams_stitch_batch.so and libams_stream.so compile too; this file says where one recording's workgroups find their chunks.
 #include "../../../include/ams_stitch.h"
+#include "stitch_core.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SLAB = 1024;            // overlap positions per workgroup of the border table
-constexpr int TILE = 960;             // words of rel staged per round of the chain walk: a multiple of every S in 1 .. 6
-
-#define STITCH_REQUIRE(cond)                   \
-    do {                                       \
-        if (!(cond)) return AMS_E_INVALID_ARG; \
-    } while (0)
-
 inline ams_status check_launch() { return hipGetLastError() == hipSuccess ? AMS_OK : AMS_E_LAUNCH_FAILED; }
-inline long cdiv(long a, long b) { return (a + b - 1) / b; }
-inline bool geometry_ok(int L, int H) { return L >= 2 && L <= (1 << 30) && H >= (L + 1) / 2 && H <= L - 1; }
-inline long chunks_of(long N, int L, int H) { return N <= L ? 1 : 1 + cdiv(N - L, H); }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// ------------------------------------------------------------------ chunks
 template <bool VEC>
 __global__ __launch_bounds__(256) void chunks_kernel(const float* __restrict__ x, long N, float* __restrict__ mix, int C, int L, int H) {
-    for (int c = blockIdx.y; c < C; c += gridDim.y) {
-        const long base = (long)c * H;
-        float* const row = mix + (long)c * L;
-        if constexpr (VEC) {
-            const int l = (blockIdx.x * 256 + threadIdx.x) * 4;
-            if (l >= L) return;
-            const long n = base + l;
-            f32x4 r;
-            if (n + 4 <= N) r = *(const f32x4*)(x + n);
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) r[e] = n + e < N ? x[n + e] : 0.f;
-            }
-            *(f32x4*)(row + l) = r;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int l = blockIdx.x * 1024 + k * 256 + threadIdx.x;
-                if (l >= L) break;
-                const long n = base + l;
-                row[l] = n < N ? x[n] : 0.f;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------ border table
-// sum of the 64 lanes in lane 0, as the halving tree l += l + o (o = 32 .. 1): one fixed order
-__device__ __forceinline__ float wave_fold(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
+    for (int c = blockIdx.y; c < C; c += gridDim.y)
+        gather_row<VEC>(x, N, (long)c * H, mix + (long)c * L, L);
 }
 
 template <int S, bool VEC>
 __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ est, float* __restrict__ part, int nb, int L, int H) {
-    __shared__ float sm[4][S * S];
-    const int V = L - H, nslab = gridDim.x, slab = blockIdx.x, tid = threadIdx.x;
+    const int V = L - H, nslab = gridDim.x, slab = blockIdx.x;
     const int v0 = slab * SLAB, v1 = min(V, v0 + SLAB);
-    for (int c = blockIdx.y; c < nb; c += gridDim.y) {
-        const float* const tail = est + (long)c * S * L + H;              // est[c, i, H + v] = tail[i L + v]
-        const float* const head = est + (long)(c + 1) * S * L;            // est[c + 1, j, v] = head[j L + v]
-        float acc[S][S];
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-#pragma unroll
-            for (int j = 0; j < S; ++j) acc[i][j] = 0.f;
-        if constexpr (VEC) {
-            const int v = v0 + tid * 4;                                    // V % 4 == 0: whole groups only
-            if (v < v1) {
-                f32x4 a[S], b[S];
-#pragma unroll
-                for (int i = 0; i < S; ++i) {
-                    a[i] = *(const f32x4*)(tail + (long)i * L + v);
-                    b[i] = *(const f32x4*)(head + (long)i * L + v);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < S; ++i)
-#pragma unroll
-                        for (int j = 0; j < S; ++j) {
-                            const float d = a[i][e] - b[j][e];
-                            acc[i][j] += d * d;
-                        }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int v = v0 + k * 256 + tid;
-                if (v < v1) {
-                    float a[S], b[S];
-#pragma unroll
-                    for (int i = 0; i < S; ++i) {
-                        a[i] = tail[(long)i * L + v];
-                        b[i] = head[(long)i * L + v];
-                    }
-#pragma unroll
-                    for (int i = 0; i < S; ++i)
-#pragma unroll
-                        for (int j = 0; j < S; ++j) {
-                            const float d = a[i] - b[j];
-                            acc[i][j] += d * d;
-                        }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-#pragma unroll
-            for (int j = 0; j < S; ++j) {
-                const float s = wave_fold(acc[i][j]);
-                if ((tid & 63) == 0) sm[tid >> 6][i * S + j] = s;
-            }
-        __syncthreads();
-        if (tid < S * S) part[((long)c * nslab + slab) * (S * S) + tid] = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
-        __syncthreads();
-    }
+    for (int c = blockIdx.y; c < nb; c += gridDim.y)                      // est[c, i, H + v] against est[c + 1, j, v]
+        border_sums<S, VEC>(est + (long)c * S * L + H, L, est + (long)(c + 1) * S * L, L, v0, v1, part + ((long)c * nslab + slab) * (S * S));
 }
 
 // Q[e] = the slab partials of entry e in slab order
@@ -133,26 +29,7 @@ __global__ __launch_bounds__(256) void stats_fold_kernel(const float* __restrict
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const long c = e / SS;
-    const int ij = (int)(e - c * SS);
-    const float* p = part + c * nslab * SS + ij;
-    float s = p[0];
-    for (int k = 1; k < nslab; ++k) s += p[(long)k * SS];
-    Q[e] = s;
-}
-
-template <int S>
-ams_status launch_stats(bool vec, dim3 grid, hipStream_t st, const float* est, float* part, int nb, int L, int H) {
-    if (vec) hipLaunchKernelGGL((stats_kernel<S, true>), grid, dim3(256), 0, st, est, part, nb, L, H);
-    else hipLaunchKernelGGL((stats_kernel<S, false>), grid, dim3(256), 0, st, est, part, nb, L, H);
-    return check_launch();
-}
-
-// ------------------------------------------------------------------ border permutations and tracks
-// (c2, p2) before (c1, p1) in the order (cost, index)?  An index >= P marks "none": a lane without a permutation, or a NaN cost.
-__device__ __forceinline__ bool goes_first(float c2, int p2, float c1, int p1, int P) {
-    if (p2 >= P) return false;
-    if (p1 >= P) return true;
-    return c2 < c1 || (c2 == c1 && p2 < p1);
+    Q[e] = slab_fold(part + c * nslab * SS + (int)(e - c * SS), nslab, SS);
 }
 
 __global__ __launch_bounds__(256) void border_perm_kernel(const float* __restrict__ Q, const int* __restrict__ perms, int* __restrict__ rel,
@@ -163,98 +40,19 @@ __global__ __launch_bounds__(256) void border_perm_kernel(const float* __restric
     const int SS = S * S, tid = threadIdx.x, c = blockIdx.x;
     if (tid < SS) q[tid] = Q[(long)c * SS + tid];
     __syncthreads();
-    float best = 0.f;
-    int bp = P;
-    for (int p = tid; p < P; p += 256) {                             // t, t + 256, t + 512: increasing index, so < keeps the lowest
-        const int* row = perms + (long)p * S;
-        float cost = 0.f;
-        for (int s = 0; s < S; ++s) cost += q[s * S + row[s]];
-        if (cost == cost && (bp == P || cost < best)) { best = cost; bp = p; }
-    }
-    sc[tid] = best;
-    sp[tid] = bp;
-    __syncthreads();
-    for (int h = 128; h >= 1; h >>= 1) {
-        if (tid < h && goes_first(sc[tid + h], sp[tid + h], sc[tid], sp[tid], P)) { sc[tid] = sc[tid + h]; sp[tid] = sp[tid + h]; }
-        __syncthreads();
-    }
-    const int win = sp[0] < P ? sp[0] : 0;                           // every cost NaN: the identity
+    const int win = best_perm(q, sc, sp, perms, S, P);
     if (tid < S) rel[(long)c * S + tid] = perms[(long)win * S + tid];
 }
 
-// one wave: trk[0, k] = k, trk[c + 1, k] = rel[c][trk[c, k]]; rel goes through LDS TILE words at a time (coalesced loads, LDS-latency chain)
 __global__ __launch_bounds__(64) void tracks_kernel(const int* __restrict__ rel, int* __restrict__ trk, int C, int S) {
-    __shared__ int sr[TILE];
-    const int lane = threadIdx.x, per = TILE / S, nb = C - 1;
-    int cur = lane < S ? lane : 0;
-    if (lane < S) trk[lane] = cur;
-    for (int b0 = 0; b0 < nb; b0 += per) {
-        const int n = min(per, nb - b0);
-        for (int w = lane; w < n * S; w += 64) sr[w] = rel[(long)b0 * S + w];
-        __syncthreads();
-        if (lane < S) {
-            for (int b = 0; b < n; ++b) {
-                cur = sr[b * S + cur];
-                trk[(long)(b0 + b + 1) * S + lane] = cur;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------ cross-fade
-__device__ __forceinline__ long chunk_of(long n, int H, int C) {
-    const long c = n / H;
-    return c < C - 1 ? c : C - 1;
+    chain_walk(rel, trk, C, S);
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ est, const int* __restrict__ trk, const float* __restrict__ w_head,
                                                   float* __restrict__ out, long N, int C, int S, int L, int H) {
-    const int k = blockIdx.y, V = L - H;
-    float* const orow = out + (long)k * N;
-    if constexpr (VEC) {
-        const long n = ((long)blockIdx.x * 256 + threadIdx.x) * 4;         // H % 4 == 0, V % 4 == 0: a group never straddles a case
-        if (n >= N) return;
-        const long c1 = chunk_of(n, H, C);
-        const long p = n - c1 * H;                                         // < L: inside chunk c1, and p + 3 < L
-        f32x4 r = *(const f32x4*)(est + (c1 * S + trk[c1 * S + k]) * L + p);
-        if (c1 > 0 && p < V) {
-            const f32x4 t = *(const f32x4*)(est + ((c1 - 1) * S + trk[(c1 - 1) * S + k]) * L + H + p);
-            const f32x4 wh = *(const f32x4*)(w_head + p);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float wt = 1.0f - wh[e];
-                const float a = wt * t[e], b = wh[e] * r[e];
-                r[e] = a + b;
-            }
-        }
-        if (n + 4 <= N) {
-            if (((uintptr_t)orow & 15) == 0) *(f32x4*)(orow + n) = r;
-            else { orow[n] = r[0]; orow[n + 1] = r[1]; orow[n + 2] = r[2]; orow[n + 3] = r[3]; }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (n + e < N) orow[n + e] = r[e];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long n = (long)blockIdx.x * 1024 + j * 256 + threadIdx.x;
-            if (n >= N) break;
-            const long c1 = chunk_of(n, H, C);
-            const long p = n - c1 * H;
-            float r = est[(c1 * S + trk[c1 * S + k]) * L + p];
-            if (c1 > 0 && p < V) {
-                const float t = est[((c1 - 1) * S + trk[(c1 - 1) * S + k]) * L + H + p];
-                const float wh = w_head[p];
-                const float wt = 1.0f - wh;
-                const float a = wt * t, b = wh * r;
-                r = a + b;
-            }
-            orow[n] = r;
-        }
-    }
+    const int k = blockIdx.y;
+    fade_block<VEC>(est, trk, w_head, out + (long)k * N, N, C, S, L, H, k, blockIdx.x);
 }
 
 }  // namespace
@@ -275,28 +73,24 @@ ams_status ams_stitch_chunks(const float* x, long N, float* mix, int C, int L, i
 }
 
 size_t ams_stitch_workspace_bytes(int C, int S, int L, int H) {
-    if (C < 2 || S < 1 || S > 6 || !geometry_ok(L, H)) return 0;
+    if (C < 2 || !sources_ok(S) || !geometry_ok(L, H)) return 0;
     return (size_t)(C - 1) * (size_t)cdiv(L - H, SLAB) * (size_t)(S * S) * sizeof(float);
 }
 
 ams_status ams_stitch_stats(const float* est, float* Q, int C, int S, int L, int H, void* ws, size_t ws_bytes, void* stream) {
     STITCH_REQUIRE(est && Q && ws);
-    STITCH_REQUIRE(S >= 1 && S <= 6 && C >= 2 && geometry_ok(L, H));
+    STITCH_REQUIRE(sources_ok(S) && C >= 2 && geometry_ok(L, H));
     if (ws_bytes < ams_stitch_workspace_bytes(C, S, L, H)) return AMS_E_WORKSPACE_TOO_SMALL;
     const int nb = C - 1, nslab = (int)cdiv(L - H, SLAB);
     const bool vec = L % 4 == 0 && H % 4 == 0 && aligned16(est);
     const dim3 grid((unsigned)nslab, (unsigned)(nb < 65535 ? nb : 65535));
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)ws;
-    ams_status rc;
-    switch (S) {
-        case 1: rc = launch_stats<1>(vec, grid, st, est, part, nb, L, H); break;
-        case 2: rc = launch_stats<2>(vec, grid, st, est, part, nb, L, H); break;
-        case 3: rc = launch_stats<3>(vec, grid, st, est, part, nb, L, H); break;
-        case 4: rc = launch_stats<4>(vec, grid, st, est, part, nb, L, H); break;
-        case 5: rc = launch_stats<5>(vec, grid, st, est, part, nb, L, H); break;
-        default: rc = launch_stats<6>(vec, grid, st, est, part, nb, L, H); break;
-    }
+    const ams_status rc = for_sources(S, [&](auto s) {
+        if (vec) hipLaunchKernelGGL((stats_kernel<s(), true>), grid, dim3(256), 0, st, est, part, nb, L, H);
+        else hipLaunchKernelGGL((stats_kernel<s(), false>), grid, dim3(256), 0, st, est, part, nb, L, H);
+        return check_launch();
+    });
     if (rc != AMS_OK) return rc;
     const long total = (long)nb * S * S;
     hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, part, Q, total, S * S, nslab);
@@ -305,10 +99,8 @@ ams_status ams_stitch_stats(const float* est, float* Q, int C, int S, int L, int
 
 ams_status ams_stitch_tracks(const float* Q, const int32_t* perms, int32_t* rel, int32_t* trk, int C, int S, int P, void* stream) {
     STITCH_REQUIRE(Q && perms && rel && trk);
-    STITCH_REQUIRE(S >= 1 && S <= 6 && C >= 2);
-    int fact = 1;
-    for (int s = 2; s <= S; ++s) fact *= s;
-    STITCH_REQUIRE(P == fact);
+    STITCH_REQUIRE(sources_ok(S) && C >= 2);
+    STITCH_REQUIRE(perm_count_ok(S, P));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(border_perm_kernel, dim3((unsigned)(C - 1)), dim3(256), 0, st, Q, perms, rel, S, P);
     ams_status rc = check_launch();
@@ -320,7 +112,7 @@ ams_status ams_stitch_tracks(const float* Q, const int32_t* perms, int32_t* rel,
 ams_status ams_stitch_ola(const float* est, const int32_t* trk, const float* w_head, float* out, long N, int C, int S, int L, int H,
                           void* stream) {
     STITCH_REQUIRE(est && trk && w_head && out);
-    STITCH_REQUIRE(S >= 1 && S <= 6 && N >= 1 && geometry_ok(L, H) && C >= 1 && (long)C == chunks_of(N, L, H));
+    STITCH_REQUIRE(sources_ok(S) && N >= 1 && geometry_ok(L, H) && C >= 1 && (long)C == chunks_of(N, L, H));
     const bool vec = L % 4 == 0 && H % 4 == 0 && aligned16(est) && aligned16(out) && aligned16(w_head);
     const dim3 grid((unsigned)cdiv(N, 1024), (unsigned)S);
     hipStream_t st = (hipStream_t)stream;

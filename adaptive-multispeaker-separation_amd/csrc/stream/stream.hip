@@ -1,26 +1,16 @@
-// Live streams (include/ams_stream.h): the stitcher of stitch.hip with its past carried in a state buffer on the device.
+// Live streams (include/ams_stream.h): the stitcher with its past carried in a state buffer on the device.
 // A library of its own (libams_stream.so): the other headers and libraries are untouched.  Built with -ffp-contract=off.  The border sums,
-// the search and the cross-fade below ARE stitch.hip's, statement for statement; what is new is where an operand lies (the row before a
-// stream's first row of a push is the tail the state carries) and where a workgroup finds its stream (a table the caller built on the
-// host; grid.z or grid.y is the entry).  Launch counts do not depend on the number of streams.  No MFMA, no atomics, no scratch; no
-// launch reads state that another workgroup of the same launch writes.
-#include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
+// the search and the fade are ../stitch/stitch_core.h's, the header that stitch.hip compiles too; what is here is where an operand lies
+// (the row before a stream's first row of a push is the tail the state carries) and where a workgroup finds its stream (a table the
+// caller built on the host; grid.z or grid.y is the entry).  Launch counts do not depend on the number of streams.  No MFMA, no
+// atomics, no scratch; no launch reads state that another workgroup of the same launch writes.
 #include "../../../include/ams_stream.h"
+#include "../stitch/stitch_core.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SLAB = 1024;            // overlap positions per workgroup of the border table
 constexpr int E = AMS_STREAM_ENTRY;
 constexpr int TRK_WORDS = 8;          // words of trk per slot of the state
-
-#define STREAM_REQUIRE(cond)                   \
-    do {                                       \
-        if (!(cond)) return AMS_E_INVALID_ARG; \
-    } while (0)
 
 long g_launches = 0;
 
@@ -28,11 +18,8 @@ inline ams_status check_launch() {
     ++g_launches;
     return hipGetLastError() == hipSuccess ? AMS_OK : AMS_E_LAUNCH_FAILED;
 }
-inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 inline int up4(int a) { return (a + 3) / 4 * 4; }
-inline bool geometry_ok(int L, int H) { return L >= 2 && L <= (1 << 30) && H >= (L + 1) / 2 && H <= L - 1; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool shape_ok(int slots, int S, int L, int H) { return slots >= 1 && slots <= 65535 && S >= 1 && S <= 6 && geometry_ok(L, H); }
+inline bool shape_ok(int slots, int S, int L, int H) { return slots >= 1 && slots <= 65535 && sources_ok(S) && geometry_ok(L, H); }
 inline bool push_ok(int slots, int n, int rows, int max_rows) {
     return n >= 1 && n <= slots && rows >= 0 && max_rows >= 0 && max_rows <= rows && max_rows <= 65535 && (long)rows <= 65535L * n;
 }
@@ -123,103 +110,24 @@ __global__ __launch_bounds__(256) void keep_kernel(State st, const int* __restri
 }
 
 // ------------------------------------------------------------------ border table
-// sum of the 64 lanes in lane 0, as the halving tree l += l + o (o = 32 .. 1): one fixed order
-__device__ __forceinline__ float wave_fold(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// stitch.hip's stats_kernel with the tail rows `ts` words apart: L inside est, Vp inside the state
+// the border in front of every row: the row before it is the carried tail (rows Vp apart) for a push's first row, est's otherwise
 template <int S, bool VEC>
 __global__ __launch_bounds__(256) void stats_kernel(State st, const int* __restrict__ table, const float* __restrict__ est,
                                                     float* __restrict__ part, int slots, int rows_total, int L, int H) {
-    __shared__ float sm[4][S * S];
     const Entry e = entry_of(table, blockIdx.z);
     if (!entry_ok(e, slots, rows_total, L)) return;                       // the same for the whole workgroup
-    const int V = L - H, nslab = gridDim.x, slab = blockIdx.x, tid = threadIdx.x;
+    const int V = L - H, nslab = gridDim.x, slab = blockIdx.x;
     const int v0 = slab * SLAB, v1 = min(V, v0 + SLAB);
     for (int j = blockIdx.y; j < e.rows; j += gridDim.y) {
         if (j == 0 && (e.flags & AMS_STREAM_FIRST)) continue;             // chunk 0: no border in front of it
         const long c = e.row0 + j;
         const float* const tail = j == 0 ? st.tail + (long)e.slot * S * st.Vp : est + (c - 1) * S * L + H;
-        const long ts = j == 0 ? st.Vp : L;
-        const float* const head = est + c * S * L;                        // est[c, j, v] = head[j L + v]
-        float acc[S][S];
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-#pragma unroll
-            for (int jj = 0; jj < S; ++jj) acc[i][jj] = 0.f;
-        if constexpr (VEC) {
-            const int v = v0 + tid * 4;                                    // V % 4 == 0: whole groups only
-            if (v < v1) {
-                f32x4 a[S], b[S];
-#pragma unroll
-                for (int i = 0; i < S; ++i) {
-                    a[i] = *(const f32x4*)(tail + i * ts + v);
-                    b[i] = *(const f32x4*)(head + (long)i * L + v);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int i = 0; i < S; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < S; ++jj) {
-                            const float d = a[i][q] - b[jj][q];
-                            acc[i][jj] += d * d;
-                        }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int v = v0 + q * 256 + tid;
-                if (v < v1) {
-                    float a[S], b[S];
-#pragma unroll
-                    for (int i = 0; i < S; ++i) {
-                        a[i] = tail[i * ts + v];
-                        b[i] = head[(long)i * L + v];
-                    }
-#pragma unroll
-                    for (int i = 0; i < S; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < S; ++jj) {
-                            const float d = a[i] - b[jj];
-                            acc[i][jj] += d * d;
-                        }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-#pragma unroll
-            for (int jj = 0; jj < S; ++jj) {
-                const float s = wave_fold(acc[i][jj]);
-                if ((tid & 63) == 0) sm[tid >> 6][i * S + jj] = s;
-            }
-        __syncthreads();
-        if (tid < S * S) part[(c * nslab + slab) * (S * S) + tid] = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
-        __syncthreads();
+        border_sums<S, VEC>(tail, j == 0 ? st.Vp : L, est + c * S * L, L, v0, v1, part + (c * nslab + slab) * (S * S));
     }
 }
 
-template <int S>
-ams_status launch_stats(bool vec, dim3 grid, hipStream_t hs, State st, const int* table, const float* est, float* part, int slots,
-                        int rows, int L, int H) {
-    if (vec) hipLaunchKernelGGL((stats_kernel<S, true>), grid, dim3(256), 0, hs, st, table, est, part, slots, rows, L, H);
-    else hipLaunchKernelGGL((stats_kernel<S, false>), grid, dim3(256), 0, hs, st, table, est, part, slots, rows, L, H);
-    return check_launch();
-}
-
 // ------------------------------------------------------------------ border permutations and tracks
-// (c2, p2) before (c1, p1) in the order (cost, index)?  An index >= P marks "none": a lane without a permutation, or a NaN cost.
-__device__ __forceinline__ bool goes_first(float c2, int p2, float c1, int p1, int P) {
-    if (p2 >= P) return false;
-    if (p1 >= P) return true;
-    return c2 < c1 || (c2 == c1 && p2 < p1);
-}
-
-// One workgroup per stream walks the stream's rows in order: Q of the row's border (the slab sums in slab order), stitch.hip's search,
+// One workgroup per stream walks the stream's rows in order: Q of the row's border (the slab sums in slab order), the search,
 // trk <- rel[trk].  tw [rows + n, S]: entry s owns rows row0 + s .. row0 + s + rows of it: the carried trk, then the trk of every row.
 __global__ __launch_bounds__(256) void track_kernel(State st, const int* __restrict__ table, const float* __restrict__ part,
                                                     const int* __restrict__ perms, int* __restrict__ tw, float* __restrict__ Q_rows,
@@ -246,29 +154,12 @@ __global__ __launch_bounds__(256) void track_kernel(State st, const int* __restr
             if (Q_rows && tid < SS) Q_rows[c * SS + tid] = 0.f;
         } else {
             if (tid < SS) {
-                const float* p = part + c * nslab * SS + tid;
-                float s = p[0];
-                for (int k = 1; k < nslab; ++k) s += p[(long)k * SS];
+                const float s = slab_fold(part + c * nslab * SS + tid, nslab, SS);
                 q[tid] = s;
                 if (Q_rows) Q_rows[c * SS + tid] = s;
             }
             __syncthreads();
-            float best = 0.f;
-            int bp = P;
-            for (int p = tid; p < P; p += 256) {                         // t, t + 256, t + 512: increasing index, so < keeps the lowest
-                const int* row = perms + (long)p * S;
-                float cost = 0.f;
-                for (int s = 0; s < S; ++s) cost += q[s * S + row[s]];
-                if (cost == cost && (bp == P || cost < best)) { best = cost; bp = p; }
-            }
-            sc[tid] = best;
-            sp[tid] = bp;
-            __syncthreads();
-            for (int h = 128; h >= 1; h >>= 1) {
-                if (tid < h && goes_first(sc[tid + h], sp[tid + h], sc[tid], sp[tid], P)) { sc[tid] = sc[tid + h]; sp[tid] = sp[tid + h]; }
-                __syncthreads();
-            }
-            win = sp[0] < P ? sp[0] : 0;                                 // every cost NaN: the identity
+            win = best_perm(q, sc, sp, perms, S, P);
         }
         int nxt = 0;
         if (tid < S) nxt = perms[(long)win * S + cur[tid]];              // (permutation 0 is the identity)
@@ -308,10 +199,7 @@ __global__ __launch_bounds__(256) void ola_kernel(State st, const int* __restric
                 if (p < V && !(j == 0 && (e.flags & AMS_STREAM_FIRST))) {
                     const int kp = mine[j * S + k];
                     const float t = j == 0 ? carried[(long)kp * st.Vp + p] : est[((c - 1) * S + kp) * L + H + p];
-                    const float wh = w_head[p];
-                    const float wt = 1.0f - wh;
-                    const float a = wt * t, b2 = wh * r;
-                    r = a + b2;
+                    r = fade(w_head[p], t, r);
                 }
             } else {
                 const long p = i - (long)e.rows * H;
@@ -354,17 +242,17 @@ size_t ams_stream_state_bytes(int slots, int S, int L, int H) {
 }
 
 ams_status ams_stream_reset(void* state, int slots, int S, int L, int H, int first, int count, void* stream) {
-    STREAM_REQUIRE(state && aligned16(state) && shape_ok(slots, S, L, H));
-    STREAM_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= slots);
+    STITCH_REQUIRE(state && aligned16(state) && shape_ok(slots, S, L, H));
+    STITCH_REQUIRE(first >= 0 && count >= 1 && (long)first + count <= slots);
     hipLaunchKernelGGL(reset_kernel, dim3((unsigned)count), dim3(256), 0, (hipStream_t)stream, carve(state, slots, S, L, H), S, first);
     return check_launch();
 }
 
 ams_status ams_stream_feed(void* state, int slots, int S, int L, int H, const int32_t* table, int n, int rows, int max_rows,
                            const float* x, long x_total, float* mix, void* stream) {
-    STREAM_REQUIRE(state && aligned16(state) && table && x && (mix || rows == 0));
-    STREAM_REQUIRE(shape_ok(slots, S, L, H) && push_ok(slots, n, rows, max_rows));
-    STREAM_REQUIRE(x_total >= 0 && x_total < (1L << 31));
+    STITCH_REQUIRE(state && aligned16(state) && table && x && (mix || rows == 0));
+    STITCH_REQUIRE(shape_ok(slots, S, L, H) && push_ok(slots, n, rows, max_rows));
+    STITCH_REQUIRE(x_total >= 0 && x_total < (1L << 31));
     const State st = carve(state, slots, S, L, H);
     hipStream_t hs = (hipStream_t)stream;
     const unsigned gx = (unsigned)cdiv(L, 1024);
@@ -377,20 +265,18 @@ ams_status ams_stream_feed(void* state, int slots, int S, int L, int H, const in
 }
 
 size_t ams_stream_workspace_bytes(int n, int rows, int S, int L, int H) {
-    if (n < 1 || rows < 0 || S < 1 || S > 6 || !geometry_ok(L, H)) return 0;
+    if (n < 1 || rows < 0 || !sources_ok(S) || !geometry_ok(L, H)) return 0;
     return ((size_t)rows * (size_t)cdiv(L - H, SLAB) * (size_t)(S * S) + ((size_t)rows + n) * S) * sizeof(float);
 }
 
 ams_status ams_stream_absorb(void* state, int slots, int S, int L, int H, const int32_t* table, int n, int rows, int max_rows, long max_m,
                              const float* est, const int32_t* perms, int P, const float* w_head, float* out, long out_stride, void* ws,
                              size_t ws_bytes, float* Q_rows, int32_t* trk_rows, void* stream) {
-    STREAM_REQUIRE(state && aligned16(state) && table && perms && w_head && out && ws && (est || rows == 0));
-    STREAM_REQUIRE(shape_ok(slots, S, L, H) && push_ok(slots, n, rows, max_rows));
-    STREAM_REQUIRE(max_m >= 0 && out_stride >= 1 && max_m <= out_stride && out_stride < (1L << 31) / S);
-    int fact = 1;
-    for (int s = 2; s <= S; ++s) fact *= s;
-    STREAM_REQUIRE(P == fact);
-    STREAM_REQUIRE(ws_bytes >= ams_stream_workspace_bytes(n, rows, S, L, H));
+    STITCH_REQUIRE(state && aligned16(state) && table && perms && w_head && out && ws && (est || rows == 0));
+    STITCH_REQUIRE(shape_ok(slots, S, L, H) && push_ok(slots, n, rows, max_rows));
+    STITCH_REQUIRE(max_m >= 0 && out_stride >= 1 && max_m <= out_stride && out_stride < (1L << 31) / S);
+    STITCH_REQUIRE(perm_count_ok(S, P));
+    STITCH_REQUIRE(ws_bytes >= ams_stream_workspace_bytes(n, rows, S, L, H));
     const State st = carve(state, slots, S, L, H);
     hipStream_t hs = (hipStream_t)stream;
     const int V = L - H, nslab = (int)cdiv(V, SLAB);
@@ -399,15 +285,11 @@ ams_status ams_stream_absorb(void* state, int slots, int S, int L, int H, const 
     const unsigned gy = (unsigned)(max_rows > 0 ? max_rows : 1);
     const bool vec = L % 4 == 0 && H % 4 == 0 && aligned16(est);
     const dim3 grid((unsigned)nslab, gy, (unsigned)n);
-    ams_status rc;
-    switch (S) {
-        case 1: rc = launch_stats<1>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-        case 2: rc = launch_stats<2>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-        case 3: rc = launch_stats<3>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-        case 4: rc = launch_stats<4>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-        case 5: rc = launch_stats<5>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-        default: rc = launch_stats<6>(vec, grid, hs, st, table, est, part, slots, rows, L, H); break;
-    }
+    ams_status rc = for_sources(S, [&](auto s) {
+        if (vec) hipLaunchKernelGGL((stats_kernel<s(), true>), grid, dim3(256), 0, hs, st, table, est, part, slots, rows, L, H);
+        else hipLaunchKernelGGL((stats_kernel<s(), false>), grid, dim3(256), 0, hs, st, table, est, part, slots, rows, L, H);
+        return check_launch();
+    });
     if (rc != AMS_OK) return rc;
     hipLaunchKernelGGL(track_kernel, dim3((unsigned)n), dim3(256), 0, hs, st, table, part, perms, tw, Q_rows, trk_rows, slots, rows, L,
                        nslab, S, P);

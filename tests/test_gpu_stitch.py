@@ -56,6 +56,27 @@ def test_border_stats_against_float64(L, H):
 
 
 @pytest.mark.parametrize('S', [1, 2, 3, 4, 5, 6])
+@pytest.mark.parametrize('L,H,base', [(16, 8, 0), (9, 5, 0), (16, 8, 4)])      # the 16-byte arm; the dword arm; the dword arm by misalignment
+def test_border_stats_every_source_count_on_every_arm(L, H, base, S):
+    """One slab, three chunks: every instantiated (S, arm) of the border sums (the slabs do not depend on S, the test above has them)."""
+    from ams_hip import stitch
+    C = 3
+    est = np.random.RandomState(100 * S + L).randn(C, S, L).astype(np.float32)
+    Q64 = ref.border_stats(est, H)
+    with Fence() as fence:
+        d = fence.dev(est, base=base)
+        Q = stitch.border_stats(d, H)
+        Q2 = stitch.border_stats(d, H)
+        fence.check()
+        q, q2 = _np(Q), _np(Q2)
+    err = np.abs(q - Q64).max() / np.abs(Q64).max()
+    print('stats S=%d L=%d H=%d base=%d: max|Q - Q64| / max|Q64| = %.3g' % (S, L, H, base, err))
+    assert q.shape == (C - 1, S, S)
+    assert err <= TOL_F64, (S, base, err)
+    assert np.array_equal(q.view(np.int32), q2.view(np.int32)), (S, base)          # the same bits from run to run
+
+
+@pytest.mark.parametrize('S', [1, 2, 3, 4, 5, 6])
 def test_tracks_match_the_restatement(S):
     from ams_hip import stitch
     L, H, C = 64, 32, 10

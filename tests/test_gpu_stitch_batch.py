@@ -140,6 +140,13 @@ def test_batch_is_bit_equal_to_every_recording_alone(L, H, S, kind):
     _compare(kind, S, L, H)
 
 
+@pytest.mark.parametrize('S', [4, 5])
+@pytest.mark.parametrize('L,H', [(16, 8), (9, 5)])                 # one slab on the 16-byte arm; one on the dword arm
+def test_four_and_five_sources_on_both_arms(L, H, S):
+    """The source counts that SOURCES leaves out, at the smallest geometry of either arm (with seeds 1000 + r the margin is >= 0.99)."""
+    _compare('eight', S, L, H)
+
+
 def test_a_misaligned_est_takes_the_dword_arm_in_both():
     _compare('eight', 2, 256, 128, base=4)
 
